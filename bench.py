@@ -19,13 +19,29 @@ optimizer passes, AdamW included.  The other BASELINE configurations are reachab
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
-The default invocation (N = 1, configs[1]) also times short legs of BASELINE configs[2] (full model, B = 32, bf16) and
-configs[4] (48 kHz inference, 64 x 10 s, bf16) and of configs[3]'s per-rank workload (48 kHz full model, bf16, batch 16,
-one rank) after the main timed region and reports them under `config.extra_configs` (`--no-extra` skips them).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line from rank 0 (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = milliseconds per timed step); every timed step of a training workload is a
+replay of the recorded batch.  `--full` adds what the headline figure does not need:
 
-Rank 0 prints ONE JSON line (contract in the task description) with `roofline` (the dominant kernel family, timed
-with HIP events attached to each dispatch on the launch stream inside the timed region) and `cpu_baseline` (the CPU
-oracle on a bounded sample of the same workload)."""
+  * `roofline` (the dominant kernel family, timed with HIP events attached to each dispatch on the launch stream on
+    every fourth timed step, which then runs eagerly) and the idle-device host-issue probe after the timed region
+    (`--no-prof` / `--no-host-probe` skip them);
+  * `cpu_baseline` (the CPU oracle on a bounded sample of the same workload; `--no-cpu-baseline` skips it);
+  * on the default configuration (N = 1, configs[1]), short legs of BASELINE configs[2] (full model, B = 32, bf16),
+    configs[4] (48 kHz inference, 64 x 10 s, bf16), configs[3]'s per-rank workload (48 kHz full model, bf16, batch 16,
+    one rank), a variable-length stream of configs[2] and the headline in the two other fp32 arithmetics, after the
+    main timed region, under `config.extra_configs` (`--no-extra` skips them).
+
+Training steps run at learning rate 0: each one computes both passes and both AdamW updates in full, but the weights
+stay at their seeded initial values, so every step starts from the same inputs.  (The split reductions combine through
+atomics; at a nonzero rate AdamW turns their rounding differences into learning-rate-sized weight changes wherever a
+gradient is near zero, and two runs would drift apart step by step.)
+
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32 / float64, well under 64 MB in
+all): training -- the losses `fit_batch` returns and a fixed, seeded sample of both optimizers' flat gradient and
+first-moment buffers after that step; inference -- a fixed, seeded sample of the decoded audio.  The inputs (initial
+weights, batches, dropout seeds) depend on the arguments only, so two runs -- and two builds -- agree output for output
+up to rounding."""
 import argparse
 import ctypes
 import glob
@@ -101,22 +117,29 @@ def parse(argv=None):
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32")
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default 16; 64 for --workload infer)")
     ap.add_argument("--frames", type=int, default=938, help="--workload infer: frames per utterance (938 = 10 s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the host-issue probe, the CPU baseline and (default configuration) the extra legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-cpu-baseline-full", action="store_true",
                     help="skip the second CPU leg (SURVEY 8d's config 1: full model, B=2)")
-    ap.add_argument("--no-prof", action="store_true", help="skip the per-launch event timing")
+    ap.add_argument("--no-prof", action="store_true", help="--full: skip the per-launch event timing")
     ap.add_argument("--no-host-probe", action="store_true",
-                    help="skip the idle-device host-issue probe after the timed region (counter-collection passes: fewer steps)")
+                    help="--full: skip the idle-device host-issue probe after the timed region (counter-collection passes: fewer steps)")
     ap.add_argument("--cpu-child", action="store_true", help=argparse.SUPPRESS)  # (internal: the CPU-baseline child process)
     ap.add_argument("--varlen", type=int, default=0, metavar="FRAMES",
                     help="--workload full: a stream of variable-length batches, padded lengths bucketed to multiples of FRAMES")
-    ap.add_argument("--no-extra", action="store_true", help="skip the short configs[2] / configs[4] legs of the default run")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the short configs[2] / configs[4] legs of the default run")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="process-group backend (gloo only with --dry-run: launcher test on a CPU-only host)")
     ap.add_argument("--dry-run", action="store_true",
                     help="start the ranks, form the process group, run the timing collectives and print the line "
                          "without launching a kernel (tests the N-rank launcher where there is no GPU)")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -379,10 +402,43 @@ def varlen_batches(cfg, B, n, seed, dev):
     return out
 
 
+# --dump-outputs: an array longer than this is written as this many of its elements (8 MB in float32), so that the five
+# large arrays of a training step (two weight buffers, two gradient buffers; audio for inference) stay below 64 MB
+DUMP_SAMPLE = 1 << 21
+
+
+def sampled(t, seed):
+    """`t` flattened, as float32 numpy: whole up to DUMP_SAMPLE elements, else one element drawn from each of DUMP_SAMPLE
+    equal slices of it by numpy's generator seeded with `seed` -- the same indices for the same length in every run."""
+    t = t.detach().reshape(-1)
+    n = t.numel()
+    if n > DUMP_SAMPLE:
+        import numpy as np
+        edges = np.arange(DUMP_SAMPLE + 1, dtype=np.int64) * n // DUMP_SAMPLE
+        idx = edges[:-1] + (np.random.default_rng(seed).random(DUMP_SAMPLE) * np.diff(edges)).astype(np.int64)
+        t = t[torch.from_numpy(idx).to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def step_outputs(out, module):
+    """What one step handed its caller, as numpy arrays by name.  Training: the losses `fit_batch` returns (float64) and
+    the flat buffers both optimizers hold after the step -- the gradients of its generator and discriminator passes and
+    the first moments its AdamW updates wrote (the weights themselves are held fixed: run_leg).  Inference: the decoded
+    audio."""
+    if module is None:
+        return {"audio": sampled(out, 0)}
+    arrays = {"loss_" + k: torch.as_tensor(v).detach().double().reshape(-1).cpu().numpy() for k, v in sorted(out.items())}
+    for name, opt in (("gen", module.optim_g), ("disc", module.optim_d)):
+        arrays[name + "_grads"] = sampled(opt.grad, 2)
+        arrays[name + "_exp_avg"] = sampled(opt.exp_avg, 3)
+    return arrays
+
+
 def run_leg(config, workload, dtype, batch, frames, steps, warmup, dev, world, rank, prof=True, f32_split=None, host_probe=True,
-            varlen=0):
+            varlen=0, dump=False):
     """Build the workload, do `warmup` untimed steps, time exactly `steps` steps between barrier + synchronize on both
-    sides, MAX over ranks.  Returns the pieces of the JSON line."""
+    sides, MAX over ranks.  Returns the pieces of the JSON line (with `dump`: also `outputs`, the last timed step's
+    results as numpy arrays, taken before anything else runs on the workload)."""
     from vcvits_amd import _lib, configs, ops, synthetic
     from vcvits_amd.light.vcvits import DEFAULT_PERIODS, VCVITS, VocoderGAN
     L = _lib.lib()
@@ -395,8 +451,12 @@ def run_leg(config, workload, dtype, batch, frames, steps, warmup, dev, world, r
     m = cfg["model"]
     torch.manual_seed(1234)  # identical initial weights on every rank
     module = None
+    last = {}  # what the latest step returned to its caller
     if infer:
-        run = build_infer(cfg, B, frames, dev)
+        step = build_infer(cfg, B, frames, dev)
+
+        def run():
+            last["out"] = step()
     else:
         if varlen:
             cfg["train"]["length_bucket_frames"] = int(varlen)  # (data/collate.py: padded lengths rounded up to multiples)
@@ -405,6 +465,12 @@ def run_leg(config, workload, dtype, batch, frames, steps, warmup, dev, world, r
         module.configure_optimizers()
         module.optim_g.broadcast_parameters()
         module.optim_d.broadcast_parameters()
+        # learning rate 0: every step still runs both passes and both AdamW updates in full, but the weights stay at their
+        # seeded initial values, so every step -- the last one included -- starts from the same inputs in every run.  At a
+        # nonzero rate the split reductions' atomics leave rounding differences in the gradients, AdamW turns them into
+        # learning-rate-sized weight changes wherever a gradient is near zero, and two runs drift apart step by step.
+        module.optim_g.set_lr(0.0)
+        module.optim_d.set_lr(0.0)
         make = synthetic.vocoder_batch if workload == "vocoder" else synthetic.full_batch
         width = m["inter_channels"] if workload == "vocoder" else m["hubert_channels"]
         if varlen:
@@ -413,7 +479,7 @@ def run_leg(config, workload, dtype, batch, frames, steps, warmup, dev, world, r
             batches = [make(B, width, seed=1234 + 17 * rank + i, device=dev) for i in range(2)]
 
         def run(i=[0]):
-            module.fit_batch(batches[i[0] % len(batches)])
+            last["out"] = module.fit_batch(batches[i[0] % len(batches)])
             i[0] += 1
 
     def sync():
@@ -494,6 +560,7 @@ def run_leg(config, workload, dtype, batch, frames, steps, warmup, dev, world, r
     c_issue = time.thread_time() - c0   # ... and the CPU time this thread spent doing it
     sync()
     dt = time.perf_counter() - t0
+    outputs = step_outputs(last["out"], module) if dump else None  # (before the host probe below steps the workload again)
     calls = (_lib.CALLS[0] - calls0) / max(steps, 1)
     bg = module.__dict__.get("_batch_graph") if module is not None else None
     n_graph = (bg.replays - replays0) if bg is not None else 0
@@ -602,7 +669,7 @@ def run_leg(config, workload, dtype, batch, frames, steps, warmup, dev, world, r
     if f32_split is not None:
         ops.set_f32_split(True, terms=6)
     torch.cuda.empty_cache()
-    return {"varlen": vstats, "arith": arith, "dt": dt, "roof": roof, "host_issue_ms": host["issue_ms"], "host": host, "calls": calls, "B": B, "cfg": cfg, "periods": periods, "config": config, "workload": workload,
+    return {"outputs": outputs, "varlen": vstats, "arith": arith, "dt": dt, "roof": roof, "host_issue_ms": host["issue_ms"], "host": host, "calls": calls, "B": B, "cfg": cfg, "periods": periods, "config": config, "workload": workload,
             "dtype": dtype, "frames": frames, "steps": steps, "warmup": warmup, "world": world, "setup_steps": setup_steps}
 
 
@@ -638,6 +705,7 @@ def make_line(r):
         wl = ("%s widths, HiFi-GAN generator + MPD(%d periods+S) + MSD + STFT/mel-L1, G step + D step + AdamW"
               % (cfgname, len(r["periods"])) if workload == "vocoder" else
               "%s full SynthesizerSVC (feature input) + MPD + MSD, G step + D step + AdamW" % cfgname)
+        wl += " (learning rate 0: weights held at their seeded initial values)"
     line.update({"n_gpus": world, "steps": steps, "warmup": r["warmup"], "ms_per_step": round(1e3 * dt / steps, 3),
                  "vs_baseline": None, "dtype": dtype, "data": "synthetic",
                  "config": {"workload": wl, "per_gpu_batch": B, "global_batch": B * world,
@@ -800,10 +868,16 @@ def main(argv=None):
         if dist.get_world_size() != world:
             raise SystemExit("bench.py: process group has %d ranks, expected %d" % (dist.get_world_size(), world))
         preflight(dev, world, rank)
-    r = run_leg(a.config, a.workload, a.dtype, a.batch, a.frames, a.steps, a.warmup, dev, world, rank, prof=not a.no_prof,
-                host_probe=not a.no_host_probe, varlen=a.varlen if a.workload == "full" else 0)
+    r = run_leg(a.config, a.workload, a.dtype, a.batch, a.frames, a.steps, a.warmup, dev, world, rank,
+                prof=a.full and not a.no_prof, host_probe=a.full and not a.no_host_probe,
+                varlen=a.varlen if a.workload == "full" else 0, dump=bool(a.dump_outputs) and rank == 0)
+    if r["outputs"] is not None:
+        import numpy as np
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in r["outputs"].items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
     line = make_line(r) if rank == 0 else None
-    default_run = (world == 1 and a.config == "base" and a.workload == "vocoder" and a.dtype == "f32"
+    default_run = (a.full and world == 1 and a.config == "base" and a.workload == "vocoder" and a.dtype == "f32"
                    and a.batch is None and not a.no_extra)
     if default_run:
         # BASELINE configs[2] and configs[4], a few steps each, so that the driver's line carries them too
@@ -835,7 +909,7 @@ def main(argv=None):
                 extra[key] = {"error": "%s: %s" % (type(e).__name__, e)}
         line["config"]["extra_configs"] = extra
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = (cpu_baseline_subprocess(a.config, a.workload, a.frames, not a.no_cpu_baseline_full)
                                     or cpu_baseline(r["cfg"], a.workload, r["periods"], a.frames,
                                                     also_full=not a.no_cpu_baseline_full))

@@ -3,7 +3,7 @@
 # Lines: eager without / with the bucket machinery, the recorded batch under DDP (three segments), the same with ONE discriminator stream, and the single-process recorded batch with one stream.
 # (--no-prof: every timed step takes the same form; bench.py records the batch in its setup phase, before the warm-up steps)
 cd "$GRAFT_REPO_ROOT"
-B="bench.py --gpus 1 --steps 12 --warmup 3 --no-cpu-baseline --no-extra --no-prof $*"
+B="bench.py --full --gpus 1 --steps 12 --warmup 3 --no-cpu-baseline --no-extra --no-prof $*"
 i=0
 for env in "VCVITS_BATCH_GRAPHS=0" "VCVITS_BATCH_GRAPHS=0 VCVITS_FORCE_DDP=1" "VCVITS_FORCE_DDP=1" "VCVITS_FORCE_DDP=1 VCVITS_STREAMS=1" "VCVITS_STREAMS=1"; do
   i=$((i+1))

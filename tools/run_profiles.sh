@@ -16,7 +16,7 @@ run() {  # name, workload key, bench flags...
   local name=$1 key=$2; shift 2
   local out=gpurun_out/$name
   rm -rf $out
-  $T 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o t -- python3 bench.py --steps 4 --warmup 4 --no-cpu-baseline --no-extra "$@" > $out.trace.log 2>&1
+  $T 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o t -- python3 bench.py --full --steps 4 --warmup 4 --no-cpu-baseline --no-extra "$@" > $out.trace.log 2>&1
   # (counter passes: eager launches only -- the discriminator step's graph replay is switched off, same kernels)
   VCVITS_GRAPHS=0 $T 420 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/fetch -o f -- python3 bench.py --steps ${PMC_STEPS:-2} --warmup ${PMC_WARMUP:-4} --no-cpu-baseline --no-extra --no-prof --no-host-probe "$@" > $out.fetch.log 2>&1
   VCVITS_GRAPHS=0 $T 420 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/write -o w -- python3 bench.py --steps ${PMC_STEPS:-2} --warmup ${PMC_WARMUP:-4} --no-cpu-baseline --no-extra --no-prof --no-host-probe "$@" > $out.write.log 2>&1
@@ -28,7 +28,7 @@ if [ -n "${ONLY:-}" ]; then
   case "$ONLY" in
     full_bf16) run ${TAG}_full_bf16 base/full/bf16 --workload full --batch 32 --dtype bf16 ;;
   esac
-  $T 400 python3 bench.py --dtype bf16 --workload full --batch 32 --steps 10 --warmup 5 --no-cpu-baseline > profiles/${TAG}_bench_line_cfg2.json 2>/dev/null
+  $T 400 python3 bench.py --full --dtype bf16 --workload full --batch 32 --steps 10 --warmup 5 --no-cpu-baseline > profiles/${TAG}_bench_line_cfg2.json 2>/dev/null
   keep
   exit 0
 fi
@@ -65,12 +65,12 @@ rm -rf gpurun_out/${TAG}_stft
 ( cd /tmp && $T 200 rocprofv3 --kernel-trace -d "$GRAFT_REPO_ROOT/gpurun_out/${TAG}_stft" -o stft -- python3 "$GRAFT_REPO_ROOT/tools/stft_bench.py" > "$GRAFT_REPO_ROOT/gpurun_out/${TAG}_stft.log" 2>&1 )
 { echo "# rocprofv3 --kernel-trace -- python3 tools/stft_bench.py: kernel-only durations by (kernel, grid); bytes: tools/stft_bench.py"; python3 tools/rocpd_kernel_times.py $(ls gpurun_out/${TAG}_stft/*.db gpurun_out/${TAG}_stft/*/*.db 2>/dev/null | head -1) stft; } > profiles/${TAG}_stft_kernels.txt 2>/dev/null
 rm -rf gpurun_out/${TAG}_stft
-$T 400 python3 bench.py --steps 10 --warmup 3 > profiles/${TAG}_bench_line.json 2> gpurun_out/${TAG}_bench.err
-$T 400 python3 bench.py --dtype bf16 --steps 10 --warmup 3 --no-cpu-baseline --no-extra > profiles/${TAG}_bench_line_bf16.json 2>/dev/null
-$T 400 python3 bench.py --dtype bf16 --workload full --batch 32 --steps 10 --warmup 5 --no-cpu-baseline > profiles/${TAG}_bench_line_cfg2.json 2>/dev/null
-$T 400 python3 bench.py --dtype bf16 --config 48k --workload full --steps 10 --warmup 5 --no-cpu-baseline > profiles/${TAG}_bench_line_cfg3_1gpu.json 2>/dev/null
-$T 400 python3 bench.py --dtype bf16 --workload full --batch 32 --varlen 64 --steps 16 --warmup 3 --no-cpu-baseline > profiles/${TAG}_bench_line_cfg2_varlen.json 2>/dev/null
-$T 400 python3 bench.py --dtype bf16 --config 48k --workload infer --steps 5 --warmup 2 > profiles/${TAG}_bench_line_cfg4.json 2>/dev/null
-$T 400 python3 bench.py --config 48k --workload infer --steps 3 --warmup 1 --no-cpu-baseline > profiles/${TAG}_bench_line_cfg4_f32.json 2>/dev/null
+$T 400 python3 bench.py --full --steps 10 --warmup 3 > profiles/${TAG}_bench_line.json 2> profiles/${TAG}_bench.err
+$T 400 python3 bench.py --full --dtype bf16 --steps 10 --warmup 3 --no-cpu-baseline --no-extra > profiles/${TAG}_bench_line_bf16.json 2>/dev/null
+$T 400 python3 bench.py --full --dtype bf16 --workload full --batch 32 --steps 10 --warmup 5 --no-cpu-baseline > profiles/${TAG}_bench_line_cfg2.json 2>/dev/null
+$T 400 python3 bench.py --full --dtype bf16 --config 48k --workload full --steps 10 --warmup 5 --no-cpu-baseline > profiles/${TAG}_bench_line_cfg3_1gpu.json 2>/dev/null
+$T 400 python3 bench.py --full --dtype bf16 --workload full --batch 32 --varlen 64 --steps 16 --warmup 3 --no-cpu-baseline > profiles/${TAG}_bench_line_cfg2_varlen.json 2>/dev/null
+$T 400 python3 bench.py --full --dtype bf16 --config 48k --workload infer --steps 5 --warmup 2 > profiles/${TAG}_bench_line_cfg4.json 2>/dev/null
+$T 400 python3 bench.py --full --config 48k --workload infer --steps 3 --warmup 1 --no-cpu-baseline > profiles/${TAG}_bench_line_cfg4_f32.json 2>/dev/null
 cp profiles/${TAG}_* gpurun_out/ 2>/dev/null
 ls profiles/ | grep ${TAG}_ | head -80
