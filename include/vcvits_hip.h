@@ -578,6 +578,34 @@ int vcv_stft_complex_fwd(const float* y, const float* window, const float* twidd
 int vcv_istft(const float* spec, const float* window, const float* twiddle, float* ola, float* out, int B, int F,
               int n_fft, int hop, int center, void* stream);
 
+/* ---- pYIN pitch tracking (csrc/pyin.hip): librosa.pyin as estimate_pitch calls it (vits/data/audio.py:24-63, from
+ * infer.py:54 / vits/data/audio.py:231 / preprocess.py:48-58), batched over utterances of different lengths.
+ * y [B, T] float32, n_samples / n_frames int32 [B] (each row framed and reflect-padded at its own length; frames past
+ * n_frames[b] are written as 0); frame_length 2048; every numpy-exact constant comes in as a table
+ * (vcvits_amd/ops/pitch.py).  nonfinite: one int the yin kernel ORs 1 into when a sample is not finite. */
+/* 1.-5. reflect padding, fp64 autocorrelation, float32 energy prefix, CMNDF and parabolic shifts
+ *       (librosa's _cumulative_mean_normalized_difference / _parabolic_interpolation): cmndf, shifts [B, Fmax, nlag] fp64,
+ *       nlag = max_period - min_period + 1 */
+int vcv_pyin_yin(const float* y, const int* n_samples, const int* n_frames, int B, int T, int Fmax, int frame_length,
+                 int hop, int pad, int min_period, int max_period, double tiny, double* cmndf, double* shifts,
+                 int* nonfinite, void* stream);
+/* 6. troughs, threshold priors and candidates (librosa's __pyin_helper) -> log(obs + tiny) [B, Fmax, 1202] fp64 and
+ *    voiced_prob [B, Fmax] fp64.  thresholds [101], beta_probs [100], gm_bonus [101] = 0.01 * sum(beta_probs[:n]),
+ *    pmf [pmf_ld, pmf_ld] = boltzmann.pmf(rank, 2, count) at [count, rank] */
+int vcv_pyin_obs(const double* cmndf, const double* shifts, const int* n_frames, int B, int Fmax, int nlag,
+                 int min_period, const double* thresholds, const double* beta_probs, const double* gm_bonus,
+                 const double* pmf, int pmf_ld, double sr, double fmin, double tiny, double log_tiny, double* log_obs,
+                 double* voiced_prob, void* stream);
+/* 7.-8. Viterbi (librosa.sequence.viterbi over kron(switch, transition_local)) and backtrace, one workgroup per
+ *       utterance.  n_states 1202; log_p_init [1202]; band [2][band_width = 91][601]: log-transition into bin t from bin
+ *       t + d - 45 of the same (0) / the other (1) voicing block; backptr: uint16 workspace [B, Fmax, 1202].  Outputs
+ *       [B, Fmax]: f0 (f0_table[601 when unvoiced]), voiced, vprob, pclass (class_table: the host's coarse_f0) and the
+ *       decoded states (NULL: not written) */
+int vcv_pyin_viterbi(const double* log_obs, const double* voiced_prob, const int* n_frames, int B, int Fmax, int n_states,
+                     const double* log_p_init, const double* band, int band_width, double log_tiny,
+                     const float* f0_table, const float* class_table, uint16_t* backptr, float* f0, uint8_t* voiced,
+                     float* vprob, float* pclass, uint16_t* states, void* stream);
+
 /* returns a static string describing the build (arch, kernel variants) */
 const char* vcv_version(void);
 /* Deterministic mode (also VCVITS_DETERMINISTIC=1): every launcher that splits a reduction over workgroups and combines

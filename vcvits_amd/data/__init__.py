@@ -1,6 +1,6 @@
 """Host-side data path of the voice-conversion trainer: batch schema + collate,
-cache-key layout of the pre-processed tensors, pitch binning and the inference length-scale plumbing.
-Pure CPU host logic, as in the reference (vits/data/*); it feeds the HIP hot path and launches no kernels."""
-from .audio import coarse_f0, infer_length_scale  # noqa: F401
+cache-key layout of the pre-processed tensors, pitch estimation and binning, and the inference length-scale plumbing,
+as in the reference (vits/data/*).  Host logic except `estimate_pitch` / `pitch_classes`, which run pYIN as HIP kernels."""
+from .audio import coarse_f0, estimate_pitch, infer_length_scale, normalize_pitch, pitch_classes  # noqa: F401
 from .collate import VoiceConversionMultiSpeakerCollate  # noqa: F401
 from .sampler import DistributedUtteranceSampler, rank_indices  # noqa: F401

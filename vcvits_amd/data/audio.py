@@ -1,9 +1,12 @@
-"""Pitch binning and inference plumbing of the data path (reference: vits/data/audio.py:65-76, infer.py:81).
+"""Pitch estimation, pitch binning and inference plumbing of the data path (reference: vits/data/audio.py:17-76,
+infer.py:81).
 
-Decoding audio files and pYIN pitch tracking stay with the reference's third-party stack (torchaudio,
-librosa: not installed here); the dataset below reads what that stack cached."""
+`estimate_pitch(method='pyin')` runs librosa.pyin's algorithm as HIP kernels (vcvits_amd/ops/pitch.py, csrc/pyin.hip); the
+pitch classes the model is conditioned on are `coarse_f0` of its result.  Decoding audio files and resampling stay with the
+reference's third-party stack (torchaudio)."""
 import math
 
+import numpy as np
 import torch
 
 
@@ -29,3 +32,74 @@ def infer_length_scale(data_hparams):
     """Frames of the target rate per source sample (infer.py:81): the `length_scale` handed to
     SynthesizerSVC.infer so the content features (source rate / 320) are resampled to target frames."""
     return (data_hparams.target_sampling_rate / data_hparams.hop_length) / data_hparams.source_sampling_rate
+
+
+def normalize_pitch(pitch, mean, std):
+    """In place, zeros kept (vits/data/audio.py:17-22)."""
+    zeros = (pitch == 0.0)
+    pitch -= mean[:, None]
+    pitch /= std[:, None]
+    pitch[zeros] = 0.0
+    return pitch
+
+
+def _pitch_args(sr, n_fft, win_length, hop_length, method, n_formants):
+    if method != "pyin":
+        raise ValueError("estimate_pitch: method=%r (only 'pyin', as the reference)" % (method,))
+    if n_formants > 1:
+        raise NotImplementedError("estimate_pitch: n_formants > 1 (the reference raises too)")
+    from ..ops.pitch import pyin_consts, _pyin_check_consts
+    _pyin_check_consts(pyin_consts(int(sr), int(win_length), int(hop_length)), int(win_length))
+    return int((n_fft - hop_length) / 2)
+
+
+def _as_wave(audio):
+    """1-D float32 tensor; host arrays are checked for finite samples here (device ones by the kernel's flag)."""
+    on_device = isinstance(audio, torch.Tensor) and audio.is_cuda
+    if isinstance(audio, torch.Tensor):
+        x = audio.detach()
+    else:
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(audio, dtype=np.float32)))
+    if x.dim() != 1:
+        raise ValueError("estimate_pitch: a 1-D waveform expected, got shape %s" % (tuple(x.shape),))
+    x = x.to(torch.float32)
+    if not on_device and not bool(torch.isfinite(x).all()):
+        raise ValueError("estimate_pitch: audio buffer is not finite everywhere")
+    return x, on_device
+
+
+def estimate_pitch(audio, sr, n_fft, win_length, hop_length, method="pyin", normalize_mean=None, normalize_std=None,
+                   n_formants=1):
+    """librosa.pyin(frame_length=win_length, hop_length, fmin=C2, fmax=C7, center=False) of `audio` reflect-padded by
+    int((n_fft - hop_length) / 2), unvoiced frames 0 (vits/data/audio.py:24-63).  1-D numpy array or tensor in; float32
+    [1, F] out, on the CPU for host input and on the input's device for device input.  The pitch tracking runs on the
+    GPU either way (there is no CPU path)."""
+    if type(normalize_mean) is float or type(normalize_mean) is list:
+        normalize_mean = torch.tensor(normalize_mean)
+    if type(normalize_std) is float or type(normalize_std) is list:
+        normalize_std = torch.tensor(normalize_std)
+    pad = _pitch_args(sr, n_fft, win_length, hop_length, method, n_formants)
+    x, on_device = _as_wave(audio)
+    from ..ops.pitch import pyin, pyin_lengths
+    pyin_lengths(None, 1, x.shape[0], int(win_length), int(hop_length), pad)  # too short: ValueError before any device work
+    dev = x.device if on_device else torch.device("cuda", torch.cuda.current_device())
+    f0, _, _, _, _ = pyin(x.to(dev).unsqueeze(0), sr=int(sr), frame_length=int(win_length), hop_length=int(hop_length),
+                          pad=pad)
+    pitch = f0 if on_device else f0.cpu()
+    if normalize_mean is not None:
+        assert normalize_std is not None
+        pitch = normalize_pitch(pitch, normalize_mean.to(pitch.device), normalize_std.to(pitch.device))
+    return pitch
+
+
+def pitch_classes(wav, lengths, sr, n_fft, win_length, hop_length=320, f0_bin=512):
+    """Batched `coarse_f0(estimate_pitch(wav[b, :lengths[b]], ...), f0_bin)`: wav [B, T] (or [B, 1, T]) on the GPU, each row
+    framed at its own length.  Returns (classes float32 [B, Fmax] on wav's device, whole numbers, 0 past a row's frames;
+    frames per row, CPU int64 [B])."""
+    pad = _pitch_args(sr, n_fft, win_length, hop_length, "pyin", 1)
+    if wav.dim() == 3 and wav.shape[1] == 1:
+        wav = wav[:, 0]
+    from ..ops.pitch import pyin
+    _, _, _, cls, n_frames = pyin(wav, lengths, sr=int(sr), frame_length=int(win_length), hop_length=int(hop_length),
+                                  pad=pad, f0_bin=int(f0_bin))
+    return cls, n_frames

@@ -2,8 +2,9 @@
 
 The reference decodes / resamples audio (torchaudio) and tracks pitch (librosa pYIN) on a cache miss and
 stores three tensors per utterance under md5-derived names.  This mirror reads that cache layout; on a miss
-it calls the `decode` hooks the caller supplies (none are bundled: the third-party stack is not part of this
-build) and stores the result under the same names, so caches are interchangeable with the reference's."""
+it calls the hooks the caller supplies and stores the result under the same names, so caches are interchangeable
+with the reference's.  Audio decoding is the caller's (`load_audio`: torchaudio in the reference); a `get_pitch` hook
+is three lines over this package's `estimate_pitch` / `coarse_f0`."""
 import hashlib
 import os
 import random
@@ -44,8 +45,8 @@ class VoiceConversionMultiSpeakerDataset(torch.utils.data.Dataset):
         if os.path.exists(path):
             return torch.load(path)
         if make is None:
-            raise FileNotFoundError("%s is not in the cache and no decoder was supplied (audio decoding / pYIN are "
-                                    "third-party steps of the reference, not part of this build)" % path)
+            raise FileNotFoundError("%s is not in the cache and no hook to make it was supplied (load_audio / "
+                                    "get_pitch)" % path)
         value = make()
         torch.save(value, path)
         return value
