@@ -606,6 +606,28 @@ int vcv_pyin_viterbi(const double* log_obs, const double* voiced_prob, const int
                      const float* f0_table, const float* class_table, uint16_t* backptr, float* f0, uint8_t* voiced,
                      float* vprob, float* pclass, uint16_t* states, void* stream);
 
+/* ---- resampling and pitch shift (csrc/audio_fx.hip): torchaudio.transforms.Resample(orig, new) with its defaults
+ * (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99; vits/data/audio.py:95-102,162-169,221-228, infer.py:39-42) and
+ * torchaudio.functional.pitch_shift (vits/data/audio.py:107,176, infer.py:46), batched.  o, n = orig / gcd, new / gcd;
+ * base = min(o, n) * 0.99; width = ceil(6 * o / base); the bank of phase p has taps k in [0, 2 * width + o). */
+/* the band of every phase, once per (o, n) and device: first [n] int32 = first tap with |t| < 6; taps [W, n] float32 =
+ * tap first[p] + w of phase p at [w][p], formed in float64 and rounded once (0 past the bank's last tap) */
+int vcv_resample_table(int o, int n, int width, int W, double base, int* first, float* taps, void* stream);
+/* y[b, i * n + p] = sum_w taps[w][p] * x[b, i * o + first[p] - width + w], fp32 FMAs in tap order; x [B, T] is zero outside
+ * [0, lens[b]) (lens NULL: T); y [B, Tout] is written everywhere, zeros from ceil(n * lens[b] / o) on.  VCV_EINVAL when
+ * the input span of one output tile does not fit in LDS (decimation by more than about 59). */
+int vcv_resample_apply(const float* x, const int* lens, float* y, int B, int T, int Tout, int o, int n, int width, int W,
+                       const int* first, const float* taps, void* stream);
+/* torchaudio.functional.phase_vocoder: spec complex64 [B, n_freq, F] interleaved (re, im) -> out [B, n_freq, F_out],
+ * F_out = ceil(F / rate); time steps float32(s * rate); phase_advance float32 [n_freq]; phase carried in float64 */
+int vcv_phase_vocoder(const float* spec, float* out, const float* phase_advance, int B, int n_freq, int F, int F_out,
+                      double rate, void* stream);
+/* torch.istft(n_fft, hop = n_fft / 4, center=True, length=) as pitch_shift calls it, power-of-two n_fft in [64, 1024]:
+ * the overlap-add sums frames in ascending order without atomics (vcv_istft's is not bit-reproducible); out [B, length],
+ * zeros past the overlap-add's end */
+int vcv_istft_ordered(const float* spec, const float* window, const float* twiddle, float* out, int B, int F, int n_fft,
+                      int length, void* stream);
+
 /* returns a static string describing the build (arch, kernel variants) */
 const char* vcv_version(void);
 /* Deterministic mode (also VCVITS_DETERMINISTIC=1): every launcher that splits a reduction over workgroups and combines

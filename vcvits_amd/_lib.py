@@ -108,6 +108,7 @@ EXPORTS = [
     "vcv_conv_bf16io_plan", "vcv_conv_bf16io_run", "vcv_cast_f32_x16", "vcv_cast_x16_f32", "vcv_conv_m1_x16_fwd",
     "vcv_prof_active", "vcv_set_seed_offset_ptr", "vcv_get_seed_offset_ptr", "vcv_pack_many_prepared", "vcv_adamw_dev", "vcv_set_words", "vcv_tuning_set", "vcv_tuning_get", "vcv_embedding_t_fwd", "vcv_embedding_t_fwd_checked", "vcv_embedding_t_bwd", "vcv_conv_x3_set_variant", "vcv_wgrad_bf16_set_force", "vcv_layernorm_c_bwd_scratch", "vcv_layernorm_c_bwd_ws", "vcv_resblock_pair_supported", "vcv_resblock_pair_pack", "vcv_resblock_pair_x16",
     "vcv_pyin_yin", "vcv_pyin_obs", "vcv_pyin_viterbi",
+    "vcv_resample_table", "vcv_resample_apply", "vcv_phase_vocoder", "vcv_istft_ordered",
 ]
 
 
@@ -241,6 +242,10 @@ _ARGTYPES = {
     "vcv_pyin_yin": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _D, _P, _P, _P, _P],
     "vcv_pyin_obs": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _D, _D, _D, _D, _P, _P, _P],
     "vcv_pyin_viterbi": [_P, _P, _P, _I, _I, _I, _P, _P, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "vcv_resample_table": [_I, _I, _I, _I, _D, _P, _P, _P],
+    "vcv_resample_apply": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "vcv_phase_vocoder": [_P, _P, _P, _I, _I, _I, _I, _D, _P],
+    "vcv_istft_ordered": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
 }
 
 

@@ -1,13 +1,16 @@
-"""Pitch estimation, pitch binning and inference plumbing of the data path (reference: vits/data/audio.py:17-76,
-infer.py:81).
+"""Audio loading, resampling, pitch shift, pitch estimation, pitch binning and inference plumbing of the data path
+(reference: vits/data/audio.py:17-76,158-239, infer.py:36-62,81).
 
 `estimate_pitch(method='pyin')` runs librosa.pyin's algorithm as HIP kernels (vcvits_amd/ops/pitch.py, csrc/pyin.hip); the
-pitch classes the model is conditioned on are `coarse_f0` of its result.  Decoding audio files and resampling stay with the
-reference's third-party stack (torchaudio)."""
+pitch classes the model is conditioned on are `coarse_f0` of its result.  `load_audio` / `get_pitch` decode WAV files on the
+host (`vcvits_amd.utils.load_wav_to_torch`) and resample on the GPU; `shift_audio` is torchaudio's pitch_shift on the GPU
+(vcvits_amd/ops/audio_fx.py, csrc/audio_fx.hip).  torchaudio is not a dependency."""
 import math
 
 import numpy as np
 import torch
+
+from ..utils import load_wav_to_torch
 
 
 def coarse_f0(f0, f0_min=50.0, f0_max=1100.0, f0_bin=512):
@@ -103,3 +106,56 @@ def pitch_classes(wav, lengths, sr, n_fft, win_length, hop_length=320, f0_bin=51
     _, _, _, cls, n_frames = pyin(wav, lengths, sr=int(sr), frame_length=int(win_length), hop_length=int(hop_length),
                                   pad=pad, f0_bin=int(f0_bin))
     return cls, n_frames
+
+
+def _current_gpu():
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _load_at(filename, sr):
+    """(samples on the CPU, or on the GPU when they were resampled there; their rate)."""
+    audio, sampling_rate = load_wav_to_torch(filename)
+    if sr is not None and sampling_rate != sr:
+        from ..ops.audio_fx import resample
+        return resample(audio.to(_current_gpu()), sampling_rate, int(sr)), int(sr)
+    return audio, sampling_rate
+
+
+def load_audio(filename, sr=None):
+    """Decoded samples of a WAV file (channels averaged), resampled to `sr` when it is given and differs from the file's rate
+    (vits/data/audio.py:158-172).  1-D float32 on the CPU, as the reference returns it; the resampling runs on the GPU."""
+    return _load_at(filename, sr)[0].cpu()
+
+
+def shift_audio(audio, sr=None, pitch_shift=0):
+    """torchaudio.functional.pitch_shift(audio, sr, pitch_shift), or `audio` itself for pitch_shift = 0
+    (vits/data/audio.py:174-180).  [T] or [B, T] float32; a CPU tensor comes back on the CPU, a device tensor stays on its
+    device.  The shift runs on the GPU either way (there is no CPU path)."""
+    if pitch_shift == 0:
+        return audio
+    if sr is None:
+        raise ValueError("shift_audio: a sampling rate is needed to shift the pitch")
+    from ..ops.audio_fx import pitch_shift as _shift
+    x = torch.as_tensor(audio)
+    if x.is_cuda:
+        return _shift(x.to(torch.float32), int(sr), pitch_shift)
+    return _shift(x.to(torch.float32).to(_current_gpu()), int(sr), pitch_shift).cpu()
+
+
+def get_pitch(filename, filter_length, win_length, num_pitch, sr=None):
+    """Pitch classes [1, F] of a WAV file at rate `sr` (the file's when None): coarse_f0(estimate_pitch(load_audio(filename,
+    sr), hop 320), f0_bin=num_pitch), on the CPU (vits/data/audio.py:213-239)."""
+    audio, sampling_rate = _load_at(filename, sr)
+    pitch = estimate_pitch(audio, sr=sampling_rate, n_fft=filter_length, win_length=win_length, hop_length=320)
+    return coarse_f0(pitch.cpu(), f0_bin=num_pitch)
+
+
+def infer_inputs(data_hparams, filename, sr=16000, pitch_shift=0):
+    """infer.py:36-62 (`get_audio`): (audio_norm [1, T], pitch classes [1, F]) of a WAV file resampled to `sr`; the classes
+    come from the audio shifted by `pitch_shift` semitones, the returned audio is the unshifted one.  Both on the CPU."""
+    audio, sampling_rate = _load_at(filename, sr)
+    audio = audio.cpu()
+    shifted = shift_audio(audio, sampling_rate, pitch_shift)
+    pitch = estimate_pitch(shifted, sr=sampling_rate, n_fft=data_hparams.filter_length, win_length=data_hparams.win_length,
+                           hop_length=320)
+    return audio.unsqueeze(0), coarse_f0(pitch)

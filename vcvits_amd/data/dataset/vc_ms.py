@@ -3,8 +3,8 @@
 The reference decodes / resamples audio (torchaudio) and tracks pitch (librosa pYIN) on a cache miss and
 stores three tensors per utterance under md5-derived names.  This mirror reads that cache layout; on a miss
 it calls the hooks the caller supplies and stores the result under the same names, so caches are interchangeable
-with the reference's.  Audio decoding is the caller's (`load_audio`: torchaudio in the reference); a `get_pitch` hook
-is three lines over this package's `estimate_pitch` / `coarse_f0`."""
+with the reference's.  `vcvits_amd.data.audio.load_audio` / `get_pitch` (WAV decoding on the host, resampling and pYIN on the
+GPU) are what a caller passes as the hooks; any callables with the reference's signatures do."""
 import hashlib
 import os
 import random
