@@ -628,6 +628,27 @@ int vcv_phase_vocoder(const float* spec, float* out, const float* phase_advance,
 int vcv_istft_ordered(const float* spec, const float* window, const float* twiddle, float* out, int B, int F, int n_fft,
                       int length, void* stream);
 
+/* ---- HuBERT inference (csrc/hubert.hip; vcvits_amd/model/hubert.py): the parts of fairseq's HubertModel.extract_features
+ * that the conv family and vcv_layernorm_c_fwd do not cover.  All tensors float32 [B, C, T], T contiguous. ---- */
+/* y[r, t] = res[r, t] + gelu(x[r, t] + bias[r % C]), exact erf GELU, r < R rows, t < T; rows of x are Tin >= T floats apart
+ * (the position conv's extra last frame is dropped here), rows of res / y T apart; bias / res may be NULL; y may be x when
+ * Tin == T */
+int vcv_hubert_bias_gelu(const float* x, const float* bias, const float* res, float* y, int R, int C, int Tin, int T,
+                         void* stream);
+/* gelu(GroupNorm(C, C)(x)): statistics per (b, c) over T, summed in float64; y may be x */
+int vcv_hubert_groupnorm_gelu(const float* x, const float* gamma, const float* beta, float* y, int B, int C, int T,
+                              float eps, void* stream);
+/* gelu(LayerNorm over C of x[b, :, t]), statistics in float64; y may be x */
+int vcv_hubert_layernorm_c_gelu(const float* x, const float* gamma, const float* beta, float* y, int B, int C, int T,
+                                float eps, void* stream);
+/* Softmax self-attention, forward only: out = softmax((scale * q)^T k) v per head; q / k / v / out [B, H*dk, T]; batch rows
+ * of q / k / v are ldb >= H*dk*T floats apart (3*H*dk*T for slices of one fused projection [B, 3*H*dk, T]).  Keys and
+ * values are streamed in tiles with a running max and sum; both contractions on the fp32 matrix cores; nothing of size
+ * T x T is stored.  vcv_hubert_attn_supported() == 0 for the shapes the kernel takes (dk 64 or 80, B*H <= 65535, any T). */
+int vcv_hubert_attn_supported(int B, int H, int dk, int T);
+int vcv_hubert_attn_fwd(const float* q, const float* k, const float* v, float* out, int B, int H, int dk, int T, int64_t ldb,
+                        float scale, void* stream);
+
 /* returns a static string describing the build (arch, kernel variants) */
 const char* vcv_version(void);
 /* Deterministic mode (also VCVITS_DETERMINISTIC=1): every launcher that splits a reduction over workgroups and combines

@@ -109,6 +109,7 @@ EXPORTS = [
     "vcv_prof_active", "vcv_set_seed_offset_ptr", "vcv_get_seed_offset_ptr", "vcv_pack_many_prepared", "vcv_adamw_dev", "vcv_set_words", "vcv_tuning_set", "vcv_tuning_get", "vcv_embedding_t_fwd", "vcv_embedding_t_fwd_checked", "vcv_embedding_t_bwd", "vcv_conv_x3_set_variant", "vcv_wgrad_bf16_set_force", "vcv_layernorm_c_bwd_scratch", "vcv_layernorm_c_bwd_ws", "vcv_resblock_pair_supported", "vcv_resblock_pair_pack", "vcv_resblock_pair_x16",
     "vcv_pyin_yin", "vcv_pyin_obs", "vcv_pyin_viterbi",
     "vcv_resample_table", "vcv_resample_apply", "vcv_phase_vocoder", "vcv_istft_ordered",
+    "vcv_hubert_bias_gelu", "vcv_hubert_groupnorm_gelu", "vcv_hubert_layernorm_c_gelu", "vcv_hubert_attn_supported", "vcv_hubert_attn_fwd",
 ]
 
 
@@ -246,6 +247,11 @@ _ARGTYPES = {
     "vcv_resample_apply": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "vcv_phase_vocoder": [_P, _P, _P, _I, _I, _I, _I, _D, _P],
     "vcv_istft_ordered": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "vcv_hubert_bias_gelu": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "vcv_hubert_groupnorm_gelu": [_P, _P, _P, _P, _I, _I, _I, _F, _P],
+    "vcv_hubert_layernorm_c_gelu": [_P, _P, _P, _P, _I, _I, _I, _F, _P],
+    "vcv_hubert_attn_supported": [_I, _I, _I, _I],
+    "vcv_hubert_attn_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _L, _F, _P],
 }
 
 

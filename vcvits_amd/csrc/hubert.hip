@@ -1,0 +1,264 @@
+// hubert.hip -- what HuBERT inference (vcvits_amd/model/hubert.py) needs beyond the conv family and layernorm_c:
+//   * softmax self-attention, forward only, keys / values streamed in tiles (no [T, T] tensor in memory);
+//   * GroupNorm(C, C) over time fused with GELU (layer 0 of the base model's conv front end);
+//   * LayerNorm over channels fused with GELU (every layer of the large models' front end);
+//   * bias + exact GELU (+ residual) as one streaming pass.
+// Everything is [B, C, T] float32 with T contiguous, as in the rest of the library.
+#include "common.h"
+#include <math.h>
+
+namespace {
+
+__device__ __forceinline__ float hubert_gelu(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// ---- y[r, t] = res[r, t] + gelu(x[r, t] + bias[r % C]) for t < T; rows of x are Tin >= T floats apart (the position
+// conv yields T + 1 frames and fairseq drops the last), rows of res / y T apart; bias / res may be null -----------------
+__global__ void __launch_bounds__(256)
+hubert_bias_gelu_kernel(const float* x, const float* __restrict__ bias, const float* res,
+                        float* y, int C, int Tin, int T, size_t n) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const size_t r = i / (size_t)T;
+  const int t = (int)(i - r * (size_t)T);
+  float v = x[r * (size_t)Tin + t];
+  if (bias) v += bias[(int)(r % (size_t)C)];
+  v = hubert_gelu(v);
+  if (res) v += res[i];
+  y[i] = v;
+}
+
+// ---- GroupNorm(C, C) + GELU: one block per (b, c) row of T samples.  Pass 1 sums x and x^2 in float64 (a row of the base
+// model's first layer has 1e5 - 1e6 samples, and a float32 sum of squares loses the variance as soon as the row has an
+// offset); pass 2 re-reads the row (from L2 while it fits), subtracts the mean as a two-float value, and writes once.
+// y may be x. -----------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+hubert_groupnorm_gelu_kernel(const float* x, const float* __restrict__ gamma, const float* __restrict__ beta, float* y,
+                             int C, int T, float eps) {
+  __shared__ double red[2][4];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const size_t row = blockIdx.x;
+  const float* xr = x + row * (size_t)T;
+  float* yr = y + row * (size_t)T;
+  // 16-byte loads over the aligned middle of the row when x and y rows are misaligned alike, scalars around it
+  int head = (int)((4 - (((uintptr_t)xr >> 2) & 3)) & 3);
+  if ((((uintptr_t)xr ^ (uintptr_t)yr) & 15) != 0 || head > T) head = T;
+  const int n4 = (T - head) >> 2, tail0 = head + 4 * n4;
+  const float4* x4 = (const float4*)(xr + head);
+  float4* y4 = (float4*)(yr + head);
+  double s = 0.0, q = 0.0;
+  for (int i = tid; i < head; i += 256) { const double a = xr[i]; s += a; q += a * a; }
+  for (int i = tid; i < n4; i += 256) {
+    const float4 v = x4[i];
+    const double a = v.x, b = v.y, c = v.z, d = v.w;
+    s += (a + b) + (c + d);
+    q += (a * a + b * b) + (c * c + d * d);
+  }
+  for (int i = tail0 + tid; i < T; i += 256) { const double a = xr[i]; s += a; q += a * a; }
+  s = wave_sum(s);
+  q = wave_sum(q);
+  if (lane == 0) { red[0][wv] = s; red[1][wv] = q; }
+  __syncthreads();
+  s = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+  q = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+  const double mean = s / T;
+  double var = q / T - mean * mean;
+  var = var > 0.0 ? var : 0.0;
+  const float mhi = (float)mean, mlo = (float)(mean - (double)mhi);
+  const int ch = (int)(row % (size_t)C);
+  const float g = (float)(1.0 / sqrt(var + (double)eps)) * gamma[ch], bt = beta[ch];
+  for (int i = tid; i < head; i += 256) yr[i] = hubert_gelu(((xr[i] - mhi) - mlo) * g + bt);
+  for (int i = tid; i < n4; i += 256) {
+    float4 v = x4[i];
+    v.x = hubert_gelu(((v.x - mhi) - mlo) * g + bt);
+    v.y = hubert_gelu(((v.y - mhi) - mlo) * g + bt);
+    v.z = hubert_gelu(((v.z - mhi) - mlo) * g + bt);
+    v.w = hubert_gelu(((v.w - mhi) - mlo) * g + bt);
+    y4[i] = v;
+  }
+  for (int i = tail0 + tid; i < T; i += 256) yr[i] = hubert_gelu(((xr[i] - mhi) - mlo) * g + bt);
+}
+
+// ---- LayerNorm over C + GELU for [B, C, T]: a block is 64 consecutive t (lanes) x 4 channel groups (waves); one pass
+// of float64 sums, one pass that normalises, activates and writes (two reads, one write).  y may be x. --------------------
+__global__ void __launch_bounds__(256)
+hubert_layernorm_c_gelu_kernel(const float* x, const float* __restrict__ gamma, const float* __restrict__ beta, float* y,
+                               int C, int T, float eps) {
+  __shared__ double red[2][4][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int b = blockIdx.y, t = blockIdx.x * 64 + lane;
+  const bool ok = t < T;
+  const size_t base = (size_t)b * C * T + (ok ? t : 0);
+  double s = 0.0, q = 0.0;
+#pragma unroll 4
+  for (int c = wv; c < C; c += 4) {
+    const double a = x[base + (size_t)c * T];
+    s += a;
+    q += a * a;
+  }
+  red[0][wv][lane] = s;
+  red[1][wv][lane] = q;
+  __syncthreads();
+  s = (red[0][0][lane] + red[0][1][lane]) + (red[0][2][lane] + red[0][3][lane]);
+  q = (red[1][0][lane] + red[1][1][lane]) + (red[1][2][lane] + red[1][3][lane]);
+  const double mean = s / C;
+  double var = q / C - mean * mean;
+  var = var > 0.0 ? var : 0.0;
+  const float mhi = (float)mean, mlo = (float)(mean - (double)mhi);
+  const float rs = (float)(1.0 / sqrt(var + (double)eps));
+  if (!ok) return;
+#pragma unroll 4
+  for (int c = wv; c < C; c += 4) {
+    const size_t o = base + (size_t)c * T;
+    y[o] = hubert_gelu(((x[o] - mhi) - mlo) * rs * gamma[c] + beta[c]);
+  }
+}
+
+// ---- softmax((q * scale)^T k) v per head, forward only.  q / k / v / out: [B, H * D, T], i.e. a head is D rows of T; batch
+// rows of q / k / v are `ldb` floats apart (H * D * T, or 3 * H * D * T when the three are slices of one fused projection).
+// A block is one head and 128 queries: each of its 4 waves owns 32 queries for the whole launch and the block streams the
+// keys / values in tiles of 32 through LDS.  Both contractions run on v_mfma_f32_32x32x2_f32 (exact fp32 products):
+//   S^T[s][t] = sum_d K[d][s] Q[d][t]   A = K tile from LDS, B = this lane's query column held in registers for the launch;
+//   O[d][t]  += sum_s V[d][s] P^T[s][t]  A = V tile from LDS, B = the S^T accumulator itself.
+// S^T leaves the matrix pipe with the query on the lane and 16 of the tile's 32 keys in the lane's registers (the other 16
+// in lane ^ 32), so the running max / sum of a query is a loop over registers plus one cross-lane exchange, and register r
+// is already the B operand of the k-pair {row(r, half 0), row(r, half 1)} of the second product: no LDS round trip for P,
+// nothing of size T x T anywhere.  D = 80 pads the value tile to 96 rows of zeros (3 output tiles of 32 channels). -------
+template <int D>
+__global__ void __launch_bounds__(256)
+hubert_attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                       float* __restrict__ out, int H, int T, size_t ldb, float scale) {
+  constexpr int DT = (D + 31) / 32;  // output tiles of 32 channels
+  constexpr int VS = 33;             // row stride of the value tile: its A fragments walk d across lanes
+  __shared__ float Ks[D * 32];
+  __shared__ float Vs[DT * 32 * VS];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int col = lane & 31, hf = lane >> 5;
+  const size_t base = (size_t)(blockIdx.y / H) * ldb + (size_t)(blockIdx.y % H) * D * T;
+  const size_t obase = (size_t)blockIdx.y * D * T;
+  const int t = blockIdx.x * 128 + wv * 32 + col;
+  const bool tok = t < T;
+
+  float qr[D / 2];
+#pragma unroll
+  for (int i = 0; i < D / 2; ++i) qr[i] = tok ? q[base + (size_t)(2 * i + hf) * T + t] * scale : 0.f;
+  for (int i = D * VS + tid; i < DT * 32 * VS; i += 256) Vs[i] = 0.f;
+
+  f32x16 o[DT];
+#pragma unroll
+  for (int j = 0; j < DT; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[j][r] = 0.f;
+  float m = -INFINITY, l = 0.f;
+
+  const int sd = tid >> 5, sc = tid & 31;
+  for (int s0 = 0; s0 < T; s0 += 32) {
+    __syncthreads();  // the previous tile has been read
+    {
+      const int s = s0 + sc;
+      const bool sok = s < T;
+#pragma unroll
+      for (int i = 0; i < D / 8; ++i) {
+        const int d = sd + 8 * i;
+        const size_t g = base + (size_t)d * T + (sok ? s : 0);
+        Ks[d * 32 + sc] = sok ? k[g] : 0.f;
+        Vs[d * VS + sc] = sok ? v[g] : 0.f;
+      }
+    }
+    __syncthreads();
+
+    f32x16 S;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) S[r] = 0.f;
+#pragma unroll
+    for (int i = 0; i < D / 2; ++i) S = __builtin_amdgcn_mfma_f32_32x32x2f32(Ks[(2 * i + hf) * 32 + col], qr[i], S, 0, 0, 0);
+
+    float mx = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int s = s0 + (r & 3) + 8 * (r >> 2) + 4 * hf;
+      if (s >= T) S[r] = -INFINITY;
+      mx = fmaxf(mx, S[r]);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    const float mn = fmaxf(m, mx);  // finite from the first tile on: key 0 exists
+    const float alpha = expf(m - mn);
+    float rs = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      S[r] = expf(S[r] - mn);
+      rs += S[r];
+    }
+    rs += __shfl_xor(rs, 32);
+    l = l * alpha + rs;
+    m = mn;
+#pragma unroll
+    for (int j = 0; j < DT; ++j) o[j] *= alpha;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int sr = (r & 3) + 8 * (r >> 2) + 4 * hf;
+#pragma unroll
+      for (int j = 0; j < DT; ++j)
+        o[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(Vs[(j * 32 + col) * VS + sr], S[r], o[j], 0, 0, 0);
+    }
+  }
+
+  if (!tok) return;
+  const float inv = 1.f / l;
+#pragma unroll
+  for (int j = 0; j < DT; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int d = j * 32 + (r & 3) + 8 * (r >> 2) + 4 * hf;
+      if (d < D) out[obase + (size_t)d * T + t] = o[j][r] * inv;
+    }
+}
+
+}  // namespace
+
+extern "C" int vcv_hubert_bias_gelu(const float* x, const float* bias, const float* res, float* y, int R, int C, int Tin,
+                                    int T, void* stream) {
+  if (!x || !y || R <= 0 || C <= 0 || T <= 0 || Tin < T) return VCV_EINVAL;
+  const size_t n = (size_t)R * T;
+  const size_t blocks = (n + 255) / 256;
+  if (blocks > 0x7fffffffULL) return VCV_EINVAL;
+  hubert_bias_gelu_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, bias, res, y, C, Tin, T, n);
+  return vcv_check_launch();
+}
+
+extern "C" int vcv_hubert_groupnorm_gelu(const float* x, const float* gamma, const float* beta, float* y, int B, int C, int T,
+                                         float eps, void* stream) {
+  if (!x || !gamma || !beta || !y || B <= 0 || C <= 0 || T <= 0) return VCV_EINVAL;
+  const long long rows = (long long)B * C;
+  if (rows > 0x7fffffffLL) return VCV_EINVAL;
+  hubert_groupnorm_gelu_kernel<<<(unsigned)rows, 256, 0, (hipStream_t)stream>>>(x, gamma, beta, y, C, T, eps);
+  return vcv_check_launch();
+}
+
+extern "C" int vcv_hubert_layernorm_c_gelu(const float* x, const float* gamma, const float* beta, float* y, int B, int C,
+                                           int T, float eps, void* stream) {
+  if (!x || !gamma || !beta || !y || B <= 0 || B > 65535 || C <= 0 || T <= 0) return VCV_EINVAL;
+  hubert_layernorm_c_gelu_kernel<<<dim3(vcv_cdiv(T, 64), B), 256, 0, (hipStream_t)stream>>>(x, gamma, beta, y, C, T, eps);
+  return vcv_check_launch();
+}
+
+extern "C" int vcv_hubert_attn_supported(int B, int H, int dk, int T) {
+  if (B <= 0 || H <= 0 || T <= 0 || (long long)B * H > 65535) return 1;
+  return (dk == 64 || dk == 80) ? 0 : 1;
+}
+
+extern "C" int vcv_hubert_attn_fwd(const float* q, const float* k, const float* v, float* out, int B, int H, int dk, int T,
+                                   int64_t ldb, float scale, void* stream) {
+  if (!q || !k || !v || !out || vcv_hubert_attn_supported(B, H, dk, T) != 0 || ldb < (int64_t)H * dk * T) return VCV_EINVAL;
+  const dim3 grid(vcv_cdiv(T, 128), B * H);
+  if (dk == 64)
+    hubert_attn_fwd_kernel<64><<<grid, 256, 0, (hipStream_t)stream>>>(q, k, v, out, H, T, (size_t)ldb, scale);
+  else
+    hubert_attn_fwd_kernel<80><<<grid, 256, 0, (hipStream_t)stream>>>(q, k, v, out, H, T, (size_t)ldb, scale);
+  return vcv_check_launch();
+}

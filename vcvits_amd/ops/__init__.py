@@ -11,6 +11,7 @@
   attention    relative-position attention
   pitch        pYIN pitch tracking (estimate_pitch's librosa.pyin): host tables, the three stage launchers, pyin()
   audio_fx     sinc resampling (torchaudio Resample), phase vocoder, ordered inverse STFT, pitch_shift()
+  hubert       HuBERT inference: streamed softmax attention, GroupNorm / LayerNorm + GELU, bias + GELU
 
 Everything runs on the GPU through hand-written HIP kernels; torch is used for buffer allocation, the current stream and
 the autograd graph only.  There is no CPU fallback: calling any op with CPU tensors raises.
@@ -20,9 +21,9 @@ the switches are one-element lists / dicts shared by reference, so `ops._USE_X3[
 To REPLACE a function (a probe or a test double) use `ops.replace(name, fn)`: the family modules call each other through
 their own globals, so an assignment on the package alone would not reach them.
 """
-from . import core, weights, conv, x16, elementwise, stft, adamw, blocks, attention, pitch, audio_fx  # noqa: F401  (dependency order)
+from . import core, weights, conv, x16, elementwise, stft, adamw, blocks, attention, pitch, audio_fx, hubert  # noqa: F401  (dependency order)
 
-FAMILIES = (core, weights, conv, x16, elementwise, stft, adamw, blocks, attention, pitch, audio_fx)
+FAMILIES = (core, weights, conv, x16, elementwise, stft, adamw, blocks, attention, pitch, audio_fx, hubert)
 for _m in FAMILIES:
     globals().update({_k: _v for _k, _v in vars(_m).items() if not _k.startswith("__")})
 del _m
