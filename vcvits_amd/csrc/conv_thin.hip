@@ -602,6 +602,7 @@ extern "C" int vcv_conv_m1_fwd(const float* x, const float* w, const float* bias
                        ntl == 1 && Tout == Tin + 2 * pad - dil * (K - 1) ? 1 : 0);
     return vcv_check_launch();
   }
+  if (K > KMAX) return VCV_EINVAL;  // (the register kernel unrolls KMAX taps: it would drop the rest)
   const int cper = vcv_cdiv(C, splits);
   if (splits > 1) {
     const size_t n = (size_t)B * U;

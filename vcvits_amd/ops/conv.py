@@ -147,7 +147,10 @@ def conv_forward(x, w, bias=None, stride=1, pad=0, dil=1, groups=1, out=None, **
         return out
     if (M == 1 and groups == 1 and C >= 16 and plain
             and kw.get("in_tf", TF_NONE) in (TF_NONE, TF_LEAKY)
-            and kw.get("out_act", ACT_NONE) in (ACT_NONE, ACT_TANH)):
+            and kw.get("out_act", ACT_NONE) in (ACT_NONE, ACT_TANH)
+            # (more than 16 taps: only the LDS-staged kernel loops over any K -- the launcher's own condition for it; the
+            # register kernel unrolls 16 and its launcher refuses the rest, which goes to the GEMM kernels below)
+            and (K <= 16 or (stride == 1 and (K - 1) * dil * P <= 256 and Tin * P < 2 ** 31 and tuning.kernel_get("m1_lds")))):
         # one output channel: HBM-bound matrix-vector kernel instead of a 32-row MFMA tile
         check(lib().vcv_conv_m1_fwd(ptr(x), ptr(w), ptr(bias), ptr(out), B, C, Tin, Tout, P, K, stride, dil, pad,
                                     1 if kw.get("in_tf", TF_NONE) == TF_LEAKY else 0, kw.get("out_act", ACT_NONE),

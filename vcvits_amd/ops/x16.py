@@ -141,6 +141,9 @@ def resblock_pair_x16(x, w1, b1, w2, b2, dil, slope=0.1, out=None, accumulate=Fa
     wp = ent["packs"].get(key) if ent is not None else None
     if wp is None:
         nbytes = lib().vcv_resblock_pair_supported(C, K, int(dil), T)
+        if nbytes <= 0:  # (declined: the pack launch below would be handed an empty buffer)
+            raise RuntimeError("vcvits_amd: the fused ResBlock pair does not take C=%d K=%d dil=%d T=%d (resblock_pair_supported)"
+                               % (C, K, int(dil), T))
         wp = torch.empty((nbytes // 4,), device=x.device, dtype=torch.float32)
         check(lib().vcv_resblock_pair_pack(ptr(w1), ptr(w2), ptr(wp), C, K, stream()), "vcv_resblock_pair_pack")
         if ent is not None:
