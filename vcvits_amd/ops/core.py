@@ -167,7 +167,9 @@ def set_deterministic(on):
     weight-gradient launch, and the library's other split reductions (thin / grouped / register-staged weight gradients,
     activation-derivative bias sums, the one-output-channel forward) run unsplit (vcv_set_deterministic).  Covers the
     GAN step of the vocoder workload (tests/test_determinism_gpu.py: two identical steps, gradients bit for bit); the
-    full model's LayerNorm-parameter and relative-position-table gradients still meet in fp32 atomics."""
+    full model's LayerNorm-parameter gradients still meet in fp32 atomics.  The relative-position-table gradients do so only
+    on the workgroup-per-tile attention backward (T > 256, or d_k other than 32 / 64) and on the unfused path; the wave-per-tile backward of the training
+    shapes sums per-tile partial tables in index order, in either mode (tests/test_attention_abi_gpu.py: two launches, same bits)."""
     _DETERMINISTIC[0] = bool(on)
     check(lib().vcv_set_deterministic(1 if on else 0), "vcv_set_deterministic")
 
