@@ -28,6 +28,10 @@
 //     group g + 1 is staged piecewise during the K stages of group g.
 //   * MFMA waves: per stage TM x 3 + TN x 3 `ds_read_b128` fragment reads feed TM x TN x NTERM MFMAs, interleaved over
 //     the wave's accumulator tiles so that consecutive MFMAs are independent.
+//   * phased launches (strided data gradients, transposed-conv forwards) of 2 or 3 output residues take the merged-phase
+//     form conv_x3_merged_kernel: one workgroup per (column tile, m-tile) for ALL residues -- the span is staged once, not
+//     once per residue, and the span fragments of a tap feed the weight slabs of every residue that has the tap (tuning key
+//     x3_merge_phases; more residues, and launches too small to fill the chip, stay one workgroup per residue).
 #include <type_traits>
 
 #include "common.h"
@@ -66,6 +70,22 @@ __device__ __forceinline__ void mma_term(f32x16 (&acc)[TM][TN], const bf16x8 (&a
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn)
       acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm][PA], b[tn][PB], acc[tm][tn], 0, 0, 0);
+}
+
+// the NTERM terms of one split product, small terms first
+template <int NTERM, int TM, int TN>
+__device__ __forceinline__ void mma_product(f32x16 (&acc)[TM][TN], const bf16x8 (&a)[TM][3], const bf16x8 (&b)[TN][3]) {
+  if (NTERM == 9) {
+    mma_term<2, 2>(acc, a, b);
+    mma_term<1, 2>(acc, a, b);
+    mma_term<2, 1>(acc, a, b);
+  }
+  mma_term<0, 2>(acc, a, b);
+  mma_term<2, 0>(acc, a, b);
+  mma_term<1, 1>(acc, a, b);
+  mma_term<0, 1>(acc, a, b);
+  mma_term<1, 0>(acc, a, b);
+  mma_term<0, 0>(acc, a, b);
 }
 
 __device__ __forceinline__ void split3(float f, __bf16& t0, __bf16& t1, __bf16& t2) {
@@ -117,6 +137,110 @@ pack_x3_kernel(const float* __restrict__ w, bf16x8* __restrict__ wp, int M, int 
 
 __device__ __forceinline__ void barrier_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+// The body of an input staging wave (xi = 0 .. NXW - 1) of a workgroup whose reduction runs S stages, NSG per channel group,
+// over the groups g_begin .. g_end - 1: one barrier after the prologue, one per stage.
+template <bool LEAKY>
+__device__ __forceinline__ void x3_stage_inputs(const VcvConvArgs& p, const BfGeom& tg, char* Xbuf, int xi, int lane, int b, int f0,
+                                                int g_begin, int g_end, int NSG, int S) {
+  const int XW = tg.xw, P = p.P, Cg = p.Cg;
+  // ---- input staging waves.  A task = (half h of the 16-channel group, block of 256 positions): 8 channels x 4
+  // consecutive positions per lane.  Wave xi owns tasks xi, xi + 3, ...; local task i of group g + 1 is converted in
+  // stage (g, i mod NSG), and its loads are issued at the START of the stage before (two register sets), so they have a
+  // whole stage to arrive.
+  const int npb = (XW + 255) >> 8;
+  const int ntask = 2 * npb;
+  const int nt_w = ntask > xi ? (ntask - xi + NXW - 1) / NXW : 0;  // tasks of this wave per group
+  const long long TinP = (long long)p.Tin * P;
+  const float* xb = p.x + (size_t)b * Cg * (size_t)TinP;
+  f32x4 xr[2][MAXT][8];
+  auto loadT = [&](int g, int i, f32x4 (&dst)[8]) __attribute__((always_inline)) {
+    const int task = xi + NXW * i;
+    const int hh = task & 1, pb = task >> 1;
+    unsigned voff = (unsigned)(f0 + pb * 256 + 4 * lane) * 4u;  // negative -> wraps -> out of range -> 0
+    asm volatile("" : "+v"(voff));  // one register (see conv_pk.hip: immediate-offset folding of negative offsets)
+    const int c0 = g * 16 + hh * 8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int c = c0 + e;
+      const unsigned rec = c < Cg ? (unsigned)(TinP * 4) : 0u;
+      __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(xb + (size_t)c * (size_t)TinP), 0, (int)rec, 0x00020000);
+      dst[e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 0));
+    }
+  };
+  auto storeT = [&](int i, const f32x4 (&src)[8], int buf) __attribute__((always_inline)) {
+    const int task = xi + NXW * i;
+    const int hh = task & 1, pb = task >> 1;
+    const int pos = pb * 256 + 4 * lane;
+    if (pos >= XW) return;  // (XW is a multiple of 64: the four positions of a lane are inside or outside together)
+    char* base = Xbuf + buf * tg.buf_bytes + ((size_t)hh * XW + pos) * 16;
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      bf16x8 v0, v1, v2;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float f = src[e][jj];
+        if (LEAKY) f = fmaxf(f, f * p.slope);  // slope in [0, 1)
+        __bf16 a, bq, d;
+        split3(f, a, bq, d);
+        v0[e] = a, v1[e] = bq, v2[e] = d;
+      }
+      *reinterpret_cast<bf16x8*>(base + (size_t)jj * 16) = v0;
+      *reinterpret_cast<bf16x8*>(base + ((size_t)2 * XW + jj) * 16) = v1;
+      *reinterpret_cast<bf16x8*>(base + ((size_t)4 * XW + jj) * 16) = v2;
+    }
+  };
+  // loads of the tasks converted in stage (g, j) -- they belong to group g + 1 -- into register set `par`
+  auto load_stage = [&](auto par, int g, int j) __attribute__((always_inline)) {
+    constexpr int PAR = decltype(par)::value;
+    if (g + 1 >= g_end) return;
+#pragma unroll
+    for (int q = 0; q < MAXT; ++q)
+      if (j + q * NSG < nt_w) loadT(g + 1, j + q * NSG, xr[PAR][q]);
+  };
+  auto store_stage = [&](auto par, int g, int j) __attribute__((always_inline)) {
+    constexpr int PAR = decltype(par)::value;
+    if (g + 1 >= g_end) return;
+    const int nb = (g + 1 - g_begin) & 1;
+#pragma unroll
+    for (int q = 0; q < MAXT; ++q)
+      if (j + q * NSG < nt_w) storeT(j + q * NSG, xr[PAR][q], nb);
+    // (more tasks per stage than the pipelined slots hold: load and convert on the spot)
+    for (int i = j + MAXT * NSG; i < nt_w; i += NSG) {
+      loadT(g + 1, i, xr[PAR][0]);
+      storeT(i, xr[PAR][0], nb);
+    }
+  };
+  typedef std::integral_constant<int, 0> P0;
+  typedef std::integral_constant<int, 1> P1;
+  // prologue: the whole span of the first group, then the loads of stage 0's tasks
+  for (int i = 0; i < nt_w; ++i) {
+    loadT(g_begin, i, xr[0][0]);
+    storeT(i, xr[0][0], 0);
+  }
+  int g = g_begin, j = 0;
+  load_stage(P0(), g, j);
+  if (xi == 0) VCV_X3_STAMP(6);
+  barrier_lds();
+  for (int s = 0; s < S; s += 2) {
+    {  // even stage: its tasks sit in set 0; the next stage's loads go to set 1
+      int g2 = g, j2 = j + 1;
+      if (j2 == NSG) j2 = 0, ++g2;
+      if (s + 1 < S) load_stage(P1(), g2, j2);
+      store_stage(P0(), g, j);
+      g = g2, j = j2;
+      barrier_lds();
+    }
+    if (s + 1 < S) {  // odd stage
+      int g2 = g, j2 = j + 1;
+      if (j2 == NSG) j2 = 0, ++g2;
+      if (s + 2 < S) load_stage(P0(), g2, j2);
+      store_stage(P1(), g, j);
+      g = g2, j = j2;
+      barrier_lds();
+    }
+  }
+}
 
 // BfGeom fields as used here: nch = channel groups of 16, a_bytes = one weight slab (3 * 2 * BM * 16), buf_bytes = one
 // span buffer (3 * 2 * xw * 16), JA / phases / ks / vec / ntu / nmt / xw as in conv_pk.hip; BKC = 16, ncg = 1.
@@ -202,103 +326,7 @@ conv_x3_kernel(const VcvConvArgs p, const BfGeom tg, const char* __restrict__ wp
       VCV_X3_STAMP(5);
       return;
     }
-    // ---- input staging waves.  A task = (half h of the 16-channel group, block of 256 positions): 8 channels x 4
-    // consecutive positions per lane.  Wave xi owns tasks xi, xi + 3, ...; local task i of group g + 1 is converted in
-    // stage (g, i mod NSG), and its loads are issued at the START of the stage before (two register sets), so they have a
-    // whole stage to arrive.
-    const int xi = pw - 1;
-    const int npb = (XW + 255) >> 8;
-    const int ntask = 2 * npb;
-    const int nt_w = ntask > xi ? (ntask - xi + NXW - 1) / NXW : 0;  // tasks of this wave per group
-    const long long TinP = (long long)p.Tin * P;
-    const float* xb = p.x + (size_t)b * Cg * (size_t)TinP;
-    f32x4 xr[2][MAXT][8];
-    auto loadT = [&](int g, int i, f32x4 (&dst)[8]) __attribute__((always_inline)) {
-      const int task = xi + NXW * i;
-      const int hh = task & 1, pb = task >> 1;
-      unsigned voff = (unsigned)(f0 + pb * 256 + 4 * lane) * 4u;  // negative -> wraps -> out of range -> 0
-      asm volatile("" : "+v"(voff));  // one register (see conv_pk.hip: immediate-offset folding of negative offsets)
-      const int c0 = g * 16 + hh * 8;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int c = c0 + e;
-        const unsigned rec = c < Cg ? (unsigned)(TinP * 4) : 0u;
-        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(xb + (size_t)c * (size_t)TinP), 0, (int)rec, 0x00020000);
-        dst[e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 0));
-      }
-    };
-    auto storeT = [&](int i, const f32x4 (&src)[8], int buf) __attribute__((always_inline)) {
-      const int task = xi + NXW * i;
-      const int hh = task & 1, pb = task >> 1;
-      const int pos = pb * 256 + 4 * lane;
-      if (pos >= XW) return;  // (XW is a multiple of 64: the four positions of a lane are inside or outside together)
-      char* base = Xbuf + buf * tg.buf_bytes + ((size_t)hh * XW + pos) * 16;
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        bf16x8 v0, v1, v2;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          float f = src[e][jj];
-          if (LEAKY) f = fmaxf(f, f * p.slope);  // slope in [0, 1)
-          __bf16 a, bq, d;
-          split3(f, a, bq, d);
-          v0[e] = a, v1[e] = bq, v2[e] = d;
-        }
-        *reinterpret_cast<bf16x8*>(base + (size_t)jj * 16) = v0;
-        *reinterpret_cast<bf16x8*>(base + ((size_t)2 * XW + jj) * 16) = v1;
-        *reinterpret_cast<bf16x8*>(base + ((size_t)4 * XW + jj) * 16) = v2;
-      }
-    };
-    // loads of the tasks converted in stage (g, j) -- they belong to group g + 1 -- into register set `par`
-    auto load_stage = [&](auto par, int g, int j) __attribute__((always_inline)) {
-      constexpr int PAR = decltype(par)::value;
-      if (g + 1 >= g_end) return;
-#pragma unroll
-      for (int q = 0; q < MAXT; ++q)
-        if (j + q * NSG < nt_w) loadT(g + 1, j + q * NSG, xr[PAR][q]);
-    };
-    auto store_stage = [&](auto par, int g, int j) __attribute__((always_inline)) {
-      constexpr int PAR = decltype(par)::value;
-      if (g + 1 >= g_end) return;
-      const int nb = (g + 1 - g_begin) & 1;
-#pragma unroll
-      for (int q = 0; q < MAXT; ++q)
-        if (j + q * NSG < nt_w) storeT(j + q * NSG, xr[PAR][q], nb);
-      // (more tasks per stage than the pipelined slots hold: load and convert on the spot)
-      for (int i = j + MAXT * NSG; i < nt_w; i += NSG) {
-        loadT(g + 1, i, xr[PAR][0]);
-        storeT(i, xr[PAR][0], nb);
-      }
-    };
-    typedef std::integral_constant<int, 0> P0;
-    typedef std::integral_constant<int, 1> P1;
-    // prologue: the whole span of the first group, then the loads of stage 0's tasks
-    for (int i = 0; i < nt_w; ++i) {
-      loadT(g_begin, i, xr[0][0]);
-      storeT(i, xr[0][0], 0);
-    }
-    int g = g_begin, j = 0;
-    load_stage(P0(), g, j);
-    if (xi == 0) VCV_X3_STAMP(6);
-    barrier_lds();
-    for (int s = 0; s < S; s += 2) {
-      {  // even stage: its tasks sit in set 0; the next stage's loads go to set 1
-        int g2 = g, j2 = j + 1;
-        if (j2 == NSG) j2 = 0, ++g2;
-        if (s + 1 < S) load_stage(P1(), g2, j2);
-        store_stage(P0(), g, j);
-        g = g2, j = j2;
-        barrier_lds();
-      }
-      if (s + 1 < S) {  // odd stage
-        int g2 = g, j2 = j + 1;
-        if (j2 == NSG) j2 = 0, ++g2;
-        if (s + 2 < S) load_stage(P0(), g2, j2);
-        store_stage(P1(), g, j);
-        g = g2, j = j2;
-        barrier_lds();
-      }
-    }
+    x3_stage_inputs<LEAKY>(p, tg, Xbuf, pw - 1, lane, b, f0, g_begin, g_end, NSG, S);
     return;
   }
 
@@ -345,18 +373,7 @@ conv_x3_kernel(const VcvConvArgs p, const BfGeom tg, const char* __restrict__ wp
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl)
               bb[tn][pl] = *reinterpret_cast<const bf16x8*>(Xs + laneoff[tn] + (size_t)pl * 2 * XW * 16);
-          // small terms first
-          if (NTERM == 9) {
-            mma_term<2, 2>(acc, a, bb);
-            mma_term<1, 2>(acc, a, bb);
-            mma_term<2, 1>(acc, a, bb);
-          }
-          mma_term<0, 2>(acc, a, bb);
-          mma_term<2, 0>(acc, a, bb);
-          mma_term<1, 1>(acc, a, bb);
-          mma_term<0, 1>(acc, a, bb);
-          mma_term<1, 0>(acc, a, bb);
-          mma_term<0, 0>(acc, a, bb);
+          mma_product<NTERM>(acc, a, bb);
         }
       }
       if (++sj == NSG) sj = 0, ++g;
@@ -368,8 +385,173 @@ conv_x3_kernel(const VcvConvArgs p, const BfGeom tg, const char* __restrict__ wp
   if (wave == 0) VCV_X3_STAMP(3);
 }
 
+// ---- merged-phase form of a phased launch (PH = 2 or 3 output residues) --------------------------------------------------
+// The residues of a phased launch read the SAME input span at the same tap offsets; only the weight slab differs (residue r
+// keeps the taps k = r + j * PH).  In the kernel above each residue is a workgroup of its own (gridDim.z), so a span is staged
+// and split PH times and multiplied by one or two taps each time.  Here ONE workgroup owns the (column tile, m-tile) for all
+// residues: the staging waves stage each channel group once, an MFMA wave holds one accumulator set per residue, and a stage
+// is one (group, tap j) for every residue that has the tap -- the span fragments of tap j are read once and multiplied by up
+// to PH weight slabs (ring slot = PH taps; residues r >= nres(j) = min(PH, K - j * PH) have no tap j: nothing is loaded or
+// multiplied for them, and a residue without any tap stores its epilogue over zeros).  Per output element the additions are
+// those of the per-residue launch in the same order (groups outer, taps inner, small terms first): the results are
+// bit-identical.  The weight pack is the one the per-residue launch reads, wp[phase][m-tile][group][tap].
+template <int nT>
+__device__ __forceinline__ void wait_vm_taps(int k) {
+  // at most k taps (nT load instructions each) stay in flight; vmcnt has six bits, and a lower count only waits longer
+  constexpr int CAP = 63 / nT;
+  switch (k) {
+    case 0: wait_vm<0>(); break;
+    case 1: wait_vm<nT>(); break;
+    case 2: wait_vm<(2 < CAP ? 2 : CAP) * nT>(); break;
+    case 3: wait_vm<(3 < CAP ? 3 : CAP) * nT>(); break;
+    case 4: wait_vm<(4 < CAP ? 4 : CAP) * nT>(); break;
+    case 5: wait_vm<(5 < CAP ? 5 : CAP) * nT>(); break;
+    default: wait_vm<(6 < CAP ? 6 : CAP) * nT>(); break;
+  }
+}
+
+template <int NTERM, int PH, int TM, int TN, int WM, int WN, bool LEAKY>
+__global__ void __launch_bounds__(64 * (WM * WN + NPROD))
+conv_x3_merged_kernel(const VcvConvArgs p, const BfGeom tg, const char* __restrict__ wp, const int nring) {
+  constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN, NW = WM * WN;
+  constexpr int TAPB = 3 * 2 * BM * 16;  // bytes of one tap of a weight slab; a ring slot (tg.a_bytes) holds PH of them
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l31 = lane & 31, h = lane >> 5;
+
+  int bx, mt, rz;  // column tile, m-tile (gridDim.z == 1: rz is 0)
+  xcd_tile_id(bx, mt, rz, tg.xcd);
+  const int b = bx / tg.ntu, ut = bx % tg.ntu;
+  const int JA = tg.JA, P = p.P, U = p.Q * P;
+  const int u0 = ut * BN, m0 = mt * BM;
+  const int qa = u0 / P;
+  const int jspan = (JA - 1) * p.dj;
+  const int jmin = jspan < 0 ? jspan : 0;
+  const int f0r = (qa * p.s + p.off + jmin) * P;
+  const int f0 = f0r & ~3;
+  const int fsh = f0r - f0;
+  const int XW = tg.xw;
+  const int S = tg.nch * JA;  // stages: (group, tap)
+  char* const Aring = smem;
+  char* const Xbuf = smem + nring * tg.a_bytes;
+
+  if (wave >= NW) {
+    // ================================================================================================ producers
+    __builtin_amdgcn_s_setprio(3);
+    const int pw = wave - NW;
+    if (pw == 0) {
+      // ---- weight DMA wave: as above, the slab of stage s + nring - 1 is issued while stage s is multiplied.  A slab has
+      // nres(j) taps, so the in-flight accounting counts taps: n1 / n2 are the taps of the last / last-but-one slab issued
+      const char* wtile = wp + (size_t)mt * tg.nch * JA * TAPB;
+      const size_t rstride = (size_t)gridDim.y * tg.nch * JA * TAPB;  // residue r + 1 of the pack
+      constexpr int nT = TAPB >> 10;  // 1 KiB wave-instructions per tap
+      auto issue = [&](int g, int j, int slot) {
+        const int nres = p.K - j * PH < PH ? p.K - j * PH : PH;
+        const char* slab = wtile + ((size_t)g * JA + j) * TAPB + lane * 16;
+        char* dst = Aring + slot * tg.a_bytes;
+#pragma unroll
+        for (int r = 0; r < PH; ++r) {
+          if (r < nres) {
+#pragma unroll
+            for (int i = 0; i < nT; ++i)
+              __builtin_amdgcn_global_load_lds((const void*)(slab + r * rstride + i * 1024), (lds_ptr)(dst + r * TAPB + i * 1024), 16, 0, 0);
+          }
+        }
+        return nres;
+      };
+      int gn = 0, jn = 0, issued = 0, slot = 0, n1 = 0, n2 = 0;
+      for (; issued < nring - 1 && issued < S; ++issued) {
+        n2 = n1, n1 = issue(gn, jn, slot);
+        if (++jn == JA) jn = 0, ++gn;
+        if (++slot == nring) slot = 0;
+      }
+      // (prologue barrier: slab 0 must be there; the ring has at most four slots)
+      wait_vm_taps<nT>(issued >= 3 ? n1 + n2 : issued == 2 ? n1 : 0);
+      asm volatile("s_barrier" ::: "memory");
+      for (int s = 0; s < S; ++s) {
+        if (issued < S) {
+          n2 = n1, n1 = issue(gn, jn, slot);
+          if (++jn == JA) jn = 0, ++gn;
+          if (++slot == nring) slot = 0;
+          ++issued;
+        }
+        // slabs <= s + 1 complete; `issued - (s + 2)` later ones may stay in flight
+        const int fly = issued - (s + 2);
+        wait_vm_taps<nT>(fly >= 2 ? n1 + n2 : fly == 1 ? n1 : 0);
+        asm volatile("s_barrier" ::: "memory");
+      }
+      return;
+    }
+    x3_stage_inputs<LEAKY>(p, tg, Xbuf, pw - 1, lane, b, f0, 0, tg.nch, JA, S);
+    return;
+  }
+
+  // ==================================================================================================== MFMA waves
+  const int wm = wave / WN, wn = wave % WN;
+  int laneoff[TN];
+#pragma unroll
+  for (int tn = 0; tn < TN; ++tn) {
+    int u = u0 + (wn * TN + tn) * 32 + l31;
+    if (u > U - 1) u = U - 1;
+    const int q = u / P, pc = u - q * P;
+    laneoff[tn] = (((q - qa) * p.s - jmin) * P + pc + fsh + h * XW) * 16;
+  }
+  f32x16 acc[PH][TM][TN];
+#pragma unroll
+  for (int r = 0; r < PH; ++r)
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[r][tm][tn][e] = 0.f;
+
+  __syncthreads();
+  {
+    const int aoff = (h * BM + wm * TM * 32 + l31) * 16;
+    int g = 0, j = 0, slot = 0;
+    for (int s = 0; s < S; ++s) {
+      const char* As0 = Aring + slot * tg.a_bytes + aoff;
+      const char* Xs = Xbuf + (g & 1) * tg.buf_bytes + j * p.dj * P * 16;
+      const int nres = p.K - j * PH < PH ? p.K - j * PH : PH;
+      bf16x8 bb[TN][3];
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl)
+          bb[tn][pl] = *reinterpret_cast<const bf16x8*>(Xs + laneoff[tn] + (size_t)pl * 2 * XW * 16);
+      // (literal residue indices: a loop the compiler leaves rolled would index the accumulator sets at run time)
+      auto residue = [&](auto rc) __attribute__((always_inline)) {
+        constexpr int r = decltype(rc)::value;
+        if (r < nres) {
+          bf16x8 a[TM][3];
+#pragma unroll
+          for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl)
+              a[tm][pl] = *reinterpret_cast<const bf16x8*>(As0 + r * TAPB + ((size_t)pl * 2 * BM + tm * 32) * 16);
+          mma_product<NTERM>(acc[r], a, bb);
+        }
+      };
+      residue(std::integral_constant<int, 0>());
+      residue(std::integral_constant<int, 1>());
+      if constexpr (PH > 2) residue(std::integral_constant<int, 2>());
+      if (++j == JA) j = 0, ++g;
+      if (++slot == nring) slot = 0;
+      __syncthreads();  // publishes stage s + 1 and retires the reads of stage s
+    }
+  }
+  // one epilogue pass per residue (output row q * os + oo + r); the shared epilogue takes its scalar path (vec = 0, ks = 1)
+  conv_tile_epilogue<TM, TN>(p, tg, acc[0], smem, nullptr, wave, wm, wn, lane, b, 0, u0, m0, p.oo, BM);
+  conv_tile_epilogue<TM, TN>(p, tg, acc[1], smem, nullptr, wave, wm, wn, lane, b, 0, u0, m0, p.oo + 1, BM);
+  if constexpr (PH > 2) conv_tile_epilogue<TM, TN>(p, tg, acc[2], smem, nullptr, wave, wm, wn, lane, b, 0, u0, m0, p.oo + 2, BM);
+}
+
 struct Plan {
   int variant, js;
+  int merged, nring;  // merged-phase form (conv_x3_merged_kernel) and its weight-ring slots
   int BM, BN, NW;
   BfGeom g;
   size_t scratch_floats, pack_bytes, lds_bytes;
@@ -386,6 +568,7 @@ bool eligible(const VcvConvArgs& a) {
 
 bool make_plan(const VcvConvArgs& a, int BM, int BN, int NW, Plan& pl, int nring = NRING_DEF, int js = 1) {
   pl.BM = BM; pl.BN = BN; pl.NW = NW;
+  pl.merged = 0; pl.nring = nring;
   BfGeom& g = pl.g;
   const int qspan = (BN - 1) / a.P + 1;
   const int adj = a.dj < 0 ? -a.dj : a.dj;
@@ -414,9 +597,26 @@ bool make_plan(const VcvConvArgs& a, int BM, int BN, int NW, Plan& pl, int nring
   return true;
 }
 
+// The merged-phase form of a phased launch: the geometry of make_plan with a ring slot of `phases` taps and the deepest ring
+// (4, 3 or 2 slots) the LDS holds next to the two span buffers; the grid has no phase dimension.
+bool make_plan_merged(const VcvConvArgs& a, int BM, int BN, int variant, Plan& pl) {
+  if (!make_plan(a, BM, BN, 8, pl, 0, 1)) return false;
+  BfGeom& g = pl.g;
+  g.a_bytes *= g.phases;
+  int nring = 4;
+  while (nring >= 2 && (size_t)nring * g.a_bytes + 2ull * g.buf_bytes > VCV_LDS_LIMIT) --nring;
+  if (nring < 2) return false;
+  pl.lds_bytes = (size_t)nring * g.a_bytes + 2ull * g.buf_bytes;
+  pl.merged = 1, pl.nring = nring, pl.variant = variant;
+  g.xcd = vcv_tuning().xcd_remap && g.nmt > 1;  // (the workgroups sharing a span are the m-tiles alone)
+  return true;
+}
+
 // variants: 0: 128x256 (8 MFMA waves of 2x2 tiles)   1: 128x128 (8 waves of 2x1)   2: 256x128 (8 waves of 2x2)   3: 64x256 (8 waves of 1x2)
 //           4: 64x128 (8 waves of 1x1)   5: 32x256 (8 waves of 1x1)   6: 64x512 (8 waves of 1x4)
 #define g_force_variant (vcv_tuning().x3_variant)  // tuning probe: -1 = choose
+#define g_all (vcv_tuning().x3_all)
+#define g_terms (vcv_tuning().x3_terms)
 int g_force_js = -1, g_force_ks = -1;
 
 bool choose(const VcvConvArgs& a, Plan& pl) {
@@ -440,6 +640,16 @@ bool choose(const VcvConvArgs& a, Plan& pl) {
     return true;
   }
   const int nph = a.phases > 1 ? a.phases : 1;
+  // Phased launches of 2 or 3 residues: one workgroup per (column tile, m-tile) computes every residue from one staged span
+  // (conv_x3_merged_kernel).  Three accumulator sets fit the register file for 2 x 1, 1 x 2 and 1 x 1 wave tiles, so the rows
+  // follow Mg as below and the columns are what those wave tiles leave.  The merged grid is 1 / phases of the per-residue one
+  // with workgroups that run all K taps per group instead of ceil(K / phases): where even the per-residue grid is no more
+  // than one round of 256 workgroups, that form finishes sooner (every tap in parallel) and keeps the launch.
+  if (vcv_tuning().x3_merge_phases && (nph == 2 || nph == 3)) {
+    const int bm = a.Mg >= 96 ? 128 : a.Mg >= 48 ? 64 : 32, bn = a.Mg >= 96 ? 128 : 256;
+    const long long nbm = (long long)a.B * vcv_cdiv(U, bn) * vcv_cdiv(a.Mg, bm);
+    if ((g_all || nbm * nph > 256) && make_plan_merged(a, bm, bn, bm == 128 ? 1 : bm == 64 ? 3 : 5, pl)) return true;
+  }
   auto blocks = [&](int bm, int bn) { return (long long)a.B * vcv_cdiv(U, bn) * vcv_cdiv(a.Mg, bm) * nph; };
   auto eff = [&](int bm, int bn) {
     const long long nb = blocks(bm, bn);
@@ -504,8 +714,6 @@ bool choose(const VcvConvArgs& a, Plan& pl) {
 // profiles/r3_x3_vs_f64.txt) the six- and nine-term results have the same error to three digits, 2e-7 .. 1e-6 of the
 // output scale -- the error of the fp32 accumulation order, as large for the fp32-input MFMA kernel -- because each left
 // out term is below 2^-24 of its product while one accumulator rounding is 2^-24 of the whole running sum.
-#define g_all (vcv_tuning().x3_all)
-#define g_terms (vcv_tuning().x3_terms)
 
 template <int NTERM, int TM, int TN, int WM, int WN, int NRING = NRING_DEF, int JS = 1>
 int launch(const VcvConvArgs& a, const Plan& pl, char* wp, float* part, int flip, bool pack_valid, hipStream_t st) {
@@ -540,8 +748,44 @@ int launch(const VcvConvArgs& a, const Plan& pl, char* wp, float* part, int flip
   return vcv_check_launch();
 }
 
+template <int NTERM, int PH, int TM, int TN, int WM, int WN>
+int launch_merged(const VcvConvArgs& a, const Plan& pl, char* wp, int flip, bool pack_valid, hipStream_t st) {
+  constexpr int BM = 32 * TM * WM, NT = 64 * (WM * WN + NPROD);
+  const BfGeom& g = pl.g;
+  if (!pack_valid) {
+    const size_t total = (size_t)g.phases * g.nmt * g.nch * g.JA * 2 * BM;
+    hipLaunchKernelGGL(pack_x3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.w, (bf16x8*)wp, a.Mg, a.Cg,
+                       a.K, BM, g.JA, g.nch, g.nmt, g.phases, 2, total);
+  }
+  void (*kern)(const VcvConvArgs, const BfGeom, const char*, int) =
+      a.in_tf == VCV_TF_LEAKY ? conv_x3_merged_kernel<NTERM, PH, TM, TN, WM, WN, true> : conv_x3_merged_kernel<NTERM, PH, TM, TN, WM, WN, false>;
+  if (pl.lds_bytes > 64 * 1024 &&
+      hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes) != hipSuccess)
+    return VCV_EHIP;
+  dim3 grid(a.B * g.ntu, g.nmt, 1), block(NT);
+  // (profiler tag and flop count of the per-residue launch: one launch, counted once)
+  const double flops = 2.0 * a.B * a.Mg * a.Cg * a.K * a.P * (double)a.Tin;
+  const int tag[12] = {a.B, 3, a.Cg, a.Mg, a.K, a.Q, a.P, a.s, g.phases, a.a_mode + 10 * g.ks, BM * 1000 + pl.BN, NTERM};
+  const double abytes = 4.0 * ((double)a.B * a.Cg * a.Tin * a.P + (double)a.Mg * a.Cg * a.K +
+                               (double)a.B * a.Mg * a.Tout * a.P * (1 + (a.res ? 1 : 0) + (a.oaux ? 1 : 0)));
+  hipEvent_t ev0, ev1;
+  vcv_prof_events(VCV_PROF_CONV_DMA, flops, tag, 12, &ev0, &ev1, abytes, NTERM * flops / VCV_PEAK_BF16_MFMA);
+  VCV_LAUNCH_EV(kern, grid, block, (unsigned)pl.lds_bytes, st, ev0, ev1, a, g, (const char*)wp, pl.nring);
+  return vcv_check_launch();
+}
+
+template <int NTERM, int PH>
+int run_merged(const VcvConvArgs& a, const Plan& pl, char* wp, int flip, bool pv, hipStream_t st) {
+  switch (pl.variant) {
+    case 1: return launch_merged<NTERM, PH, 2, 1, 2, 4>(a, pl, wp, flip, pv, st);  // 128 x 128
+    case 3: return launch_merged<NTERM, PH, 1, 2, 2, 4>(a, pl, wp, flip, pv, st);  // 64 x 256
+    default: return launch_merged<NTERM, PH, 1, 1, 1, 8>(a, pl, wp, flip, pv, st);  // 32 x 256
+  }
+}
+
 template <int NTERM>
 int run_n(const VcvConvArgs& a, const Plan& pl, char* wp, float* part, int flip, bool pv, hipStream_t st) {
+  if (pl.merged) return pl.g.phases == 2 ? run_merged<NTERM, 2>(a, pl, wp, flip, pv, st) : run_merged<NTERM, 3>(a, pl, wp, flip, pv, st);
   switch (pl.variant) {
     case 0: return pl.js == 2 ? launch<NTERM, 2, 2, 2, 4, NRING_DEF, 2>(a, pl, wp, part, flip, pv, st)
                               : launch<NTERM, 2, 2, 2, 4>(a, pl, wp, part, flip, pv, st);

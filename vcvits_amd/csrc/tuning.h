@@ -19,6 +19,7 @@ struct VcvTuning {
   int x3_variant = -1;     // split-operand kernel: fix the tile variant 0..6 (-1: the planner's choice)
   int x3_v6 = 1;           // 64 x 512 tile for the generator's 64-channel layers
   int x3_js2 = 1;          // two taps per stage where the doubled weight ring fits
+  int x3_merge_phases = 1;  // phased launches of 2 / 3 residues: one workgroup computes all residues of its tile
   int x3_old_ks = 0;       // round-3 rule for the channel-group split
   int x3_all = 0;          // take every eligible launch, not only the shapes where the split kernel is ahead
   int x3_terms = 6;        // bf16 product terms per fp32 product: 6 or 9
