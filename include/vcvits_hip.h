@@ -198,6 +198,16 @@ int vcv_conv_x3_get_terms(void);
 int vcv_conv_x3_set_all(int all);
 /* tuning probe: fix the tile variant (0..6; -1 = the library's choice), taps per stage (1 | 2) and channel-group split (>= 2 | -1) */
 int vcv_conv_x3_set_variant(int variant, int js, int ks);
+/* What the planner of one packed-weight family decides for a launch (host-only, like the *_plan entries; tests pin it).
+ * family: 0 vcv_conv_dma_*, 1 vcv_conv_pk_*, 2 vcv_conv_bf16_*, 3 vcv_conv_x3_*, 4 vcv_conv_bf16io_*.  Returns what the family's
+ * *_plan returns for (args, flip); on success out16 =
+ *   [0] tile variant as launched   [1] BM (tile rows)   [2] BN (tile columns)   [3] threads per workgroup
+ *   [4] BKC (reduction channels per chunk)   [5] JA (taps per residue)   [6] phases   [7] nch (chunks)
+ *   [8] ks (workgroups a tile's reduction is split over)   [9] vec (16-byte epilogue)   [10] xcd (XCD-aware tile order)
+ *   [11] dynamic LDS bytes   [12] taps per stage (x3) / input positions per lane and load (pk, bf16, bf16io) / 0 (dma)
+ *   [13] weight-ring slots (x3) / LDS buffers (the others)   [14] 1: all phases in one launch (x3 merged kernel, bf16io ms > 1)
+ *   [15] xw (staged input span per channel, elements) */
+int vcv_conv_plan_describe(const VcvConvArgs* args, int family, int flip, int32_t* out16);
 
 /*
  * Weight gradient of the same family (torch autograd of the call sites above):

@@ -567,7 +567,7 @@ def test_x3_forced_variant(gpu, p):
 
 # What the plan signature (vcv_conv_x3_plan: pack words, scratch floats, BM, taps per phase, phases) can show of a switch is
 # asserted: x3_old_ks changes the scratch, xcd_remap / pk_vec change nothing.  It carries neither the column width of the tile nor
-# the taps per stage, so for x3_js2 and x3_v6 the conditions of choose() are restated on the test's shape instead (_x3_choice).
+# the taps per stage, so for x3_js2 and x3_v6 the planner is asked which variant the test's shape reaches (_x3_choice).
 # x3_js2 = 0 acts on variants 0 / 1 only.  X3_A's forward (320 output channels, U = 300) is planned as variant 2 (256 x 128) and
 # does not read the switch; its data gradient (256 output channels) is planned as variant 0 (128 x 256) and loses its second tap
 # per stage under it: the switch is checked through dx.
@@ -592,18 +592,16 @@ def test_x3_switch(gpu, p):
 
 
 def _x3_choice(B, Mg, U, v6=True):
-    """The tile variant conv_x3.hip's choose() plans for a stride-1, one-phase launch of Mg output channels and U columns."""
-    cdiv = lambda a, b: -(-a // b)
-    blocks = lambda bm, bn: B * cdiv(U, bn) * cdiv(Mg, bm)
-    eff = lambda bm, bn: (U / (cdiv(U, bn) * bn)) * (Mg / (cdiv(Mg, bm) * bm)) * (blocks(bm, bn) / (cdiv(blocks(bm, bn), 256) * 256))
-    if Mg >= 96:
-        e256, e128 = (eff(128, 256) if U > 160 else 0.0), eff(128, 128)
-        return 0 if e256 >= e128 - 0.02 and e256 > 0 else 2 if Mg >= 256 and eff(256, 128) >= e128 - 0.1 else 1
-    if Mg >= 48:
-        if v6 and blocks(64, 256) > 256 and blocks(64, 512) >= 192 and eff(64, 512) >= eff(64, 256) - 0.02:
-            return 6
-        return 3 if U > 160 and eff(64, 256) >= eff(64, 128) - 0.02 else 4
-    return 5
+    """The tile variant conv_x3.hip's choose() plans for a stride-1, one-phase launch of Mg output channels and U columns, as
+    vcv_conv_plan_describe reports it (host-only; 64 input channels and 3 taps: every variant's LDS image fits)."""
+    from vcvits_amd._lib import VcvConvArgs, lib
+    a = VcvConvArgs()
+    a.B, a.G, a.Cg, a.Mg, a.Tin, a.Tout, a.P, a.K = B, 1, 64, Mg, U, U, 1, 3
+    a.s, a.dj, a.off, a.os, a.oo, a.phases, a.Q, a.alpha = 1, 1, -1, 1, 0, 1, U, 1.0
+    words = (ctypes.c_int32 * 16)()
+    with f32_split(True, all_shapes=True), switched("x3_v6", 1 if v6 else 0):
+        assert lib().vcv_conv_plan_describe(ctypes.byref(a), 3, 0, words) == 0
+    return words[0]
 
 
 def test_x3_choice_of_the_switch_shapes():

@@ -17,6 +17,7 @@
 //     it is read from LDS (two VALU ops per fragment element).
 #include "common.h"
 #include "prof.h"
+#include "conv_plan.h"
 
 namespace {
 
@@ -291,24 +292,13 @@ struct Plan {
   size_t ws_floats, pack_floats, lds_bytes;
 };
 
-bool eligible(const VcvConvArgs& a) {
-  const bool fwd_type = a.a_mode == 0 && a.phases <= 1;
-  const bool phased = a.a_mode == 1 && a.phases > 1 && a.s == 1 && a.dj == -1;
-  return (fwd_type || phased) && a.G == 1 && a.io == 0 && a.post_scale == 0.f && a.ms <= 1 && (a.in_tf == VCV_TF_NONE || (a.in_tf == VCV_TF_LEAKY && a.slope < 1.f && a.slope >= 0.f)) &&
-         a.Mg >= 32 && a.Cg >= 16 && a.K <= 16 && a.s >= 1 && (long long)a.Tin * a.P * 4 < (1ll << 31) &&
-         (long long)a.Mg * a.Tout * a.P < (1ll << 31);
-}
+bool eligible(const VcvConvArgs& a) { return conv_eligible(a, false); }  // (dword staging: any stride)
 
 bool make_plan(const VcvConvArgs& a, int BM, int BN, Plan& pl) {
   pl.BM = BM; pl.BN = BN;
   DmaGeom& g = pl.g;
-  const int qspan = (BN - 1) / a.P + 1;
-  const int adj = a.dj < 0 ? -a.dj : a.dj;
-  g.phases = a.phases > 1 ? a.phases : 1;
-  g.JA = vcv_cdiv(a.K, g.phases);
-  const int rowmax = (qspan * a.s + (g.JA - 1) * adj + 1) * a.P;
-  const int xw = (rowmax + 63) & ~63;
-  g.xw = xw;
+  conv_span(a, BM, BN, 0, g);
+  const int xw = g.xw;
   // chunk: ~64 (c, tap) rows, even channel count, KKR*BM a multiple of 256 floats, two buffers within ~120 KiB
   int bkc = 64 / g.JA;
   bkc &= ~1;
@@ -329,8 +319,6 @@ bool make_plan(const VcvConvArgs& a, int BM, int BN, Plan& pl) {
   g.BKC = bkc;
   g.KKR = bkc * g.JA;
   g.nch = vcv_cdiv(a.Cg, bkc);
-  g.ntu = vcv_cdiv(a.Q * a.P, BN);
-  g.nmt = vcv_cdiv(a.Mg, BM);
   g.a_floats = g.KKR * BM;
   g.buf_floats = g.a_floats + bkc * xw;
   pl.lds_bytes = 2ull * g.buf_floats * 4;
@@ -351,8 +339,8 @@ bool choose(const VcvConvArgs& a, Plan& pl) {
   const bool pointwise_ok = a.K <= 2 && a.Cg * a.K >= 128;
   bool normal_ok = a.phases > 1 ? (a.K >= 4 && U >= 160) : ((a.K >= (a.Mg <= 64 ? 3 : 5) || pointwise_ok) && U >= 160);
   if (!normal_ok && (a.phases > 1 || (a.K < 3 && !pointwise_ok) || U < 128)) return false;
-  const int nph = a.phases > 1 ? a.phases : 1;
-  auto blocks = [&](int bm, int bn) { return (long long)a.B * vcv_cdiv(U, bn) * vcv_cdiv(a.Mg, bm) * nph; };
+  const int nph = conv_phases(a);
+  auto blocks = [&](int bm, int bn) { return conv_blocks(a, bm, bn); };
   if (normal_ok && U > 160 && U <= 224) {
     if (a.Mg >= 128 && blocks(128, 224) >= (nph > 1 ? 128 : 224) && make_plan(a, 128, 224, pl)) { pl.variant = 2; return true; }
     if (a.Mg >= 64 && blocks(64, 224) >= (a.Mg >= 128 ? 192 : 1) && make_plan(a, 64, 224, pl)) { pl.variant = 3; return true; }
@@ -394,8 +382,9 @@ bool choose(const VcvConvArgs& a, Plan& pl) {
 }
 
 template <int TM, int TN, int WM, int WN>
-int launch(const VcvConvArgs& a, const Plan& pl, float* ws, float* part, bool pack_valid, hipStream_t st) {
+int launch(const VcvConvArgs& a, const Plan& pl, float* ws, float* part, bool pack_valid, hipStream_t st, int32_t* desc) {
   constexpr int BM = 32 * TM * WM, NT = 64 * WM * WN;
+  if (desc) { desc[3] = NT; return VCV_OK; }  // vcv_conv_plan_describe: the instantiation this launch would run
   const DmaGeom& g = pl.g;
   // pack (forward orientation; the data-gradient orientation is packed by the caller through flip)
   const size_t plds = (size_t)g.KKR * (BM + 1) * 4;
@@ -412,25 +401,10 @@ int launch(const VcvConvArgs& a, const Plan& pl, float* ws, float* part, bool pa
   }
   void (*kern)(const VcvConvArgs, const DmaGeom, const float*, float*) =
       a.in_tf == VCV_TF_LEAKY ? conv_dma_kernel<TM, TN, WM, WN, true> : conv_dma_kernel<TM, TN, WM, WN, false>;
-  if (pl.lds_bytes > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes) != hipSuccess)
-    return VCV_EHIP;
   VcvConvArgs aa = a;
   aa.accumulate = a.accumulate & 1;
-  dim3 grid(a.B * g.ntu * g.ks, g.nmt, g.phases), block(NT);
-  const double flops = 2.0 * a.B * a.Mg * a.Cg * a.K * a.P * (double)(g.phases > 1 ? a.Tin : a.Q);
-  const int tag[12] = {a.B, 1, a.Cg, a.Mg, a.K, a.Q, a.P, a.s, g.phases, a.a_mode + 10 * g.ks, BM * 1000 + pl.BN, g.BKC};
-  hipEvent_t ev0, ev1;
-  // algorithmic bytes: input once, weights once, output once (+ the fused epilogue operands)
-  const double abytes = 4.0 * ((double)a.B * a.Cg * a.Tin * a.P + (double)a.Mg * a.Cg * a.K +
-                               (double)a.B * a.Mg * a.Tout * a.P * (1 + (a.res ? 1 : 0) + (a.oaux ? 1 : 0)));
-  vcv_prof_events(VCV_PROF_CONV_DMA, flops, tag, 12, &ev0, &ev1, abytes);
-  VCV_LAUNCH_EV(kern, grid, block, (unsigned)pl.lds_bytes, st, ev0, ev1, aa, g, (const float*)ws, part);
-  if (g.ks > 1) {
-    const size_t n = (size_t)a.B * a.Mg * a.Q * a.P;
-    hipLaunchKernelGGL(conv_dma_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, aa, (const float*)part, g.ks);
-  }
-  return vcv_check_launch();
+  return conv_launch_tail(kern, aa, g, dim3(a.B * g.ntu * g.ks, g.nmt, g.phases), NT, pl.lds_bytes, st, {1, BM * 1000 + pl.BN, g.BKC},
+                          conv_abytes(a, 4.0, false), 0, (const float*)ws, part, conv_dma_finish_kernel);
 }
 
 }  // namespace
@@ -444,11 +418,11 @@ extern "C" int64_t vcv_conv_dma_workspace(const VcvConvArgs* args) {
 }
 
 namespace {
-int run(const VcvConvArgs* args, float* pack_ws, float* scratch_ws, int flip, bool pack_valid, void* stream) {
-  if (!args || !pack_ws || !eligible(*args)) return VCV_EINVAL;
+int run(const VcvConvArgs* args, float* pack_ws, float* scratch_ws, int flip, bool pack_valid, void* stream, int32_t* desc = nullptr) {
+  if (!args || (!pack_ws && !desc) || !eligible(*args)) return VCV_EINVAL;
   Plan pl;
   if (!choose(*args, pl)) return VCV_EINVAL;
-  if (pl.g.ks > 1 && !scratch_ws) return VCV_EINVAL;
+  if (pl.g.ks > 1 && !scratch_ws && !desc) return VCV_EINVAL;
   VcvConvArgs a = *args;
   a.accumulate = (a.accumulate & 1) | (flip ? 256 : 0);
   hipStream_t st = (hipStream_t)stream;
@@ -458,17 +432,22 @@ int run(const VcvConvArgs* args, float* pack_ws, float* scratch_ws, int flip, bo
   if (pl.variant == 1) pl.variant = 21;  // 128x256 with 16 waves
   if (pl.variant == 3) pl.variant = 23;  // 64x224 with 14 waves
   if (pl.variant == 5) pl.variant = 25;  // 64x128 with 8 waves
+  if (desc) {
+    const DmaGeom& g = pl.g;
+    const int32_t d[16] = {pl.variant, pl.BM, pl.BN, 0, g.BKC, g.JA, g.phases, g.nch, g.ks, 0, 0, (int32_t)pl.lds_bytes, 0, 2, 0, g.xw};
+    for (int i = 0; i < 16; ++i) desc[i] = d[i];
+  }
   switch (pl.variant) {
-    case 0: return launch<2, 2, 2, 2>(a, pl, pack_ws, scratch_ws, pack_valid, st);
-    case 2: return launch<4, 1, 1, 7>(a, pl, pack_ws, scratch_ws, pack_valid, st);
-    case 4: return launch<2, 2, 1, 4>(a, pl, pack_ws, scratch_ws, pack_valid, st);
-    case 8: return launch<2, 1, 2, 4>(a, pl, pack_ws, scratch_ws, pack_valid, st);
-    case 9: return launch<4, 1, 1, 9>(a, pl, pack_ws, scratch_ws, pack_valid, st);
-    case 12: return launch<2, 1, 2, 7>(a, pl, pack_ws, scratch_ws, pack_valid, st);
-    case 16: return launch<1, 1, 1, 8>(a, pl, pack_ws, scratch_ws, pack_valid, st);
-    case 21: return launch<2, 1, 2, 8>(a, pl, pack_ws, scratch_ws, pack_valid, st);
-    case 23: return launch<1, 1, 2, 7>(a, pl, pack_ws, scratch_ws, pack_valid, st);
-    default: return launch<1, 1, 2, 4>(a, pl, pack_ws, scratch_ws, pack_valid, st);
+    case 0: return launch<2, 2, 2, 2>(a, pl, pack_ws, scratch_ws, pack_valid, st, desc);
+    case 2: return launch<4, 1, 1, 7>(a, pl, pack_ws, scratch_ws, pack_valid, st, desc);
+    case 4: return launch<2, 2, 1, 4>(a, pl, pack_ws, scratch_ws, pack_valid, st, desc);
+    case 8: return launch<2, 1, 2, 4>(a, pl, pack_ws, scratch_ws, pack_valid, st, desc);
+    case 9: return launch<4, 1, 1, 9>(a, pl, pack_ws, scratch_ws, pack_valid, st, desc);
+    case 12: return launch<2, 1, 2, 7>(a, pl, pack_ws, scratch_ws, pack_valid, st, desc);
+    case 16: return launch<1, 1, 1, 8>(a, pl, pack_ws, scratch_ws, pack_valid, st, desc);
+    case 21: return launch<2, 1, 2, 8>(a, pl, pack_ws, scratch_ws, pack_valid, st, desc);
+    case 23: return launch<1, 1, 2, 7>(a, pl, pack_ws, scratch_ws, pack_valid, st, desc);
+    default: return launch<1, 1, 2, 4>(a, pl, pack_ws, scratch_ws, pack_valid, st, desc);
   }
 }
 }  // namespace
@@ -496,6 +475,11 @@ extern "C" int vcv_conv_dma_plan(const VcvConvArgs* args, int flip, int64_t* out
   const DmaGeom& g = pl.g;
   out[2] = ((int64_t)pl.BM << 40) | ((int64_t)g.BKC << 28) | ((int64_t)g.JA << 20) | ((int64_t)g.phases << 8) | (flip ? 1 : 0);
   return 0;
+}
+
+// vcv_conv_plan_describe, family 0 (the words are listed in include/vcvits_hip.h)
+extern "C" __attribute__((visibility("hidden"))) int vcv_conv_describe_dma(const VcvConvArgs* args, int flip, int32_t* out16) {
+  return run(args, nullptr, nullptr, flip, true, nullptr, out16);
 }
 
 extern "C" int vcv_conv_dma_run(const VcvConvArgs* args, float* pack_ws, float* scratch_ws, int flip, int pack_valid,

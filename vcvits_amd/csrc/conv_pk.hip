@@ -43,6 +43,13 @@ extern "C" int vcv_conv_bf16_run(const VcvConvArgs* args, float* pack_ws, float*
                                  void* stream) {
   return run_t<Bf16El>(args, pack_ws, scratch_ws, flip, pack_valid, stream);
 }
+// vcv_conv_plan_describe, families 1 and 2
+extern "C" __attribute__((visibility("hidden"))) int vcv_conv_describe_pk(const VcvConvArgs* args, int flip, int32_t* out16) {
+  return run_t<F32El>(args, nullptr, nullptr, flip, 1, nullptr, out16);
+}
+extern "C" __attribute__((visibility("hidden"))) int vcv_conv_describe_bf16(const VcvConvArgs* args, int flip, int32_t* out16) {
+  return run_t<Bf16El>(args, nullptr, nullptr, flip, 1, nullptr, out16);
+}
 // The same kernel on fp32 elements (4-channel 16-byte groups, v_mfma_f32_32x32x2_f32: exact fp32)
 extern "C" int vcv_conv_pk_plan(const VcvConvArgs* args, int flip, int64_t* out) { return plan_t<F32El>(args, flip, out); }
 extern "C" int vcv_conv_pk_run(const VcvConvArgs* args, float* pack_ws, float* scratch_ws, int flip, int pack_valid,

@@ -155,6 +155,30 @@ extern "C" int vcv_conv_bf16io_run(const VcvConvArgs* args, float* pack_ws, floa
   }
 }
 
+// What the planner of `family` (0 dma, 1 pk, 2 bf16, 3 x3, 4 bf16io) decides for a launch: returns what the family's _plan
+// returns and on success fills the sixteen words include/vcvits_hip.h lists.  Host-only, like the _plan entries.
+extern "C" __attribute__((visibility("hidden"))) int vcv_conv_describe_dma(const VcvConvArgs*, int, int32_t*);
+extern "C" __attribute__((visibility("hidden"))) int vcv_conv_describe_pk(const VcvConvArgs*, int, int32_t*);
+extern "C" __attribute__((visibility("hidden"))) int vcv_conv_describe_bf16(const VcvConvArgs*, int, int32_t*);
+extern "C" __attribute__((visibility("hidden"))) int vcv_conv_describe_x3(const VcvConvArgs*, int, int32_t*);
+extern "C" int vcv_conv_plan_describe(const VcvConvArgs* args, int family, int flip, int32_t* out16) {
+  if (!args || !out16) return VCV_EINVAL;
+  switch (family) {
+    case 0: return vcv_conv_describe_dma(args, flip, out16);
+    case 1: return vcv_conv_describe_pk(args, flip, out16);
+    case 2: return vcv_conv_describe_bf16(args, flip, out16);
+    case 3: return vcv_conv_describe_x3(args, flip, out16);
+    case 4:
+      switch (args->io) {
+        case 3: return vcv_conv_io_describe_3(args, flip, out16);
+        case 7: return vcv_conv_io_describe_7(args, flip, out16);
+        case 11: return vcv_conv_io_describe_11(args, flip, out16);
+        case 15: return vcv_conv_io_describe_15(args, flip, out16);
+      }
+  }
+  return VCV_EINVAL;
+}
+
 // kind: 1 = bf16, 2 = fp16 (the storage kinds of conv_tile.h)
 extern "C" int vcv_cast_f32_x16(const float* x, void* y, int64_t n, int kind, void* stream) {
   if (!x || !y || n <= 0 || (kind != 1 && kind != 2) || (((uintptr_t)x | (uintptr_t)y) & 15)) return VCV_EINVAL;

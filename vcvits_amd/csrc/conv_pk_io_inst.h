@@ -8,7 +8,8 @@
 #define VCV_IO_CAT(a, b) VCV_IO_CAT2(a, b)
 #define VCV_IO_DECL(io)                                                                                              \
   __attribute__((visibility("hidden"))) int VCV_IO_CAT(vcv_conv_io_plan_, io)(const VcvConvArgs*, int, int64_t*);   \
-  __attribute__((visibility("hidden"))) int VCV_IO_CAT(vcv_conv_io_run_, io)(const VcvConvArgs*, float*, float*, int, int, void*);
+  __attribute__((visibility("hidden"))) int VCV_IO_CAT(vcv_conv_io_run_, io)(const VcvConvArgs*, float*, float*, int, int, void*); \
+  __attribute__((visibility("hidden"))) int VCV_IO_CAT(vcv_conv_io_describe_, io)(const VcvConvArgs*, int, int32_t*);
 VCV_IO_DECL(3)
 VCV_IO_DECL(7)
 VCV_IO_DECL(11)
@@ -21,5 +22,8 @@ int VCV_IO_CAT(vcv_conv_io_plan_, VCV_IO_INST)(const VcvConvArgs* args, int flip
 int VCV_IO_CAT(vcv_conv_io_run_, VCV_IO_INST)(const VcvConvArgs* args, float* pack_ws, float* scratch_ws, int flip, int pack_valid,
                                                void* stream) {
   return run_t<Bf16El, VCV_IO_INST>(args, pack_ws, scratch_ws, flip, pack_valid, stream);
+}
+int VCV_IO_CAT(vcv_conv_io_describe_, VCV_IO_INST)(const VcvConvArgs* args, int flip, int32_t* out16) {
+  return run_t<Bf16El, VCV_IO_INST>(args, nullptr, nullptr, flip, 1, nullptr, out16);
 }
 #endif

@@ -5,6 +5,7 @@
 #include "common.h"
 #include "prof.h"
 #include "conv_tile.h"  // BfGeom, conv_tile_epilogue, conv_pk_finish*_kernel
+#include "conv_plan.h"
 
 namespace {
 
@@ -344,18 +345,9 @@ constexpr int MAXT_X4 = 2;   // ... of 4 x CPG loaded floats each, with 16-byte 
 constexpr int MAXT_X4_WS = 4;
 
 bool eligible(const VcvConvArgs& a, int io = 0) {
-  if (a.io != io || (io == 0 && a.post_scale != 0.f)) return false;
   if (io != 0 && (a.out_tf != VCV_TF_NONE || (((long long)a.Tin * a.P) & 1) || (((long long)a.Tout * a.P) & 1) || a.xaux || a.oaux))
     return false;  // bf16 tensors: rows of an even number of elements (4-byte aligned), no derivative masks
-  const bool fwd_type = a.a_mode == 0 && a.phases <= 1 && a.ms <= 1;
-  const bool phased = a.a_mode == 1 && a.phases > 1 && a.s == 1 && a.dj == -1 && a.ms <= 1;
-  // all output phases of a transposed conv as rows of one launch (16-bit activations only: the epilogue that interleaves them)
-  const bool merged = io != 0 && a.ms > 1 && a.a_mode == 1 && a.phases <= 1 && a.s == 1 && a.dj == -1 && a.os == a.ms && a.P == 1 &&
-                      a.Mg % a.ms == 0 && !a.res && !a.mask && !a.accumulate;
-  return (fwd_type || phased || merged) && a.G == 1 &&
-         (a.in_tf == VCV_TF_NONE || (a.in_tf == VCV_TF_LEAKY && a.slope < 1.f && a.slope >= 0.f)) && a.Mg >= 32 &&
-         a.Cg >= 16 && a.K <= 16 && a.s >= 1 && a.s <= 3 && (long long)a.Tin * a.P * 4 < (1ll << 31) &&
-         (long long)a.Mg * a.Tout * a.P < (1ll << 31);
+  return conv_eligible(a, true, io);
 }
 
 template <class EL>
@@ -366,12 +358,7 @@ bool make_plan(const VcvConvArgs& a, int BM, int BN, int NW, Plan& pl, int NS = 
   pl.BM = BM; pl.BN = BN; pl.NW = NW; pl.ppl = ppl;
   const bool x4 = ppl > 1;
   BfGeom& g = pl.g;
-  const int qspan = (BN - 1) / a.P + 1;
-  const int adj = a.dj < 0 ? -a.dj : a.dj;
-  g.phases = a.phases > 1 ? a.phases : 1;
-  g.JA = vcv_cdiv(a.K, g.phases);
-  const int rowmax = (qspan * a.s + (g.JA - 1) * adj + 1) * a.P;
-  g.xw = (rowmax + (ppl - 1) + 63) & ~63;  // (up to ppl - 1 elements of round-down at the start)
+  conv_span(a, BM, BN, ppl - 1, g);  // (up to ppl - 1 elements of round-down at the start)
   // chunk depth: 16-channel groups per chunk.  Candidates must fit two LDS buffers (one when a single chunk covers the
   // reduction) and MAXT staging tasks per wave; among them the least zero-padded channel count wins, then the deeper.
   const int cmax = ((a.Cg + KG - 1) / KG) * KG;
@@ -396,18 +383,13 @@ bool make_plan(const VcvConvArgs& a, int BM, int BN, int NW, Plan& pl, int NS = 
   g.BKC = bkc;
   g.ncg = bkc / KG;
   g.nch = vcv_cdiv(a.Cg, bkc);
-  g.ntu = vcv_cdiv(a.Q * a.P, BN);
-  g.nmt = vcv_cdiv(a.Mg, BM);
   g.a_bytes = g.JA * bkc * BM * ESZ;
   g.buf_bytes = g.a_bytes + bkc * g.xw * ESZ;
   pl.lds_bytes = (g.nch > 1 ? 2ull : 1ull) * g.buf_bytes;  // one chunk: no second buffer, more workgroups per CU
   if (pl.lds_bytes > VCV_LDS_LIMIT) return false;
   g.ks = 1;
   g.vec = 0;
-  const int xcd_remap = vcv_tuning().xcd_remap;
-  // nothing to share when a column tile has one workgroup (measured: the re-deal alone costs the 64 x 10 s decode 11 %:
-  // eight XCDs walking eight far-apart regions of the tensor instead of one)
-  g.xcd = xcd_remap && g.nmt * (g.phases > 1 ? g.phases : 1) > 1;
+  g.xcd = conv_xcd(g.nmt * g.phases);
   pl.pack_bytes = (size_t)g.phases * g.nmt * g.nch * g.a_bytes;
   pl.scratch_floats = 0;
   return true;
@@ -417,19 +399,15 @@ bool make_plan(const VcvConvArgs& a, int BM, int BN, int NW, Plan& pl, int NS = 
 //           3: 64x256 / 8 waves (1x2... 2x4 waves of 1x2)   4: 64x128 / 8 waves (1x1)   5: 32x256 / 8 waves (1x1)
 //           6: 64x224 / 14 waves (1x1)   7: 128x288 / 9 waves (4x1)   16: 64x288 / 9 waves (2x1)
 //           12 / 13: warp-specialised 128x256 (8 + 4 waves) / 128x224 (4 + 4 waves)
-template <class EL, int IO = 0>
-bool choose(const VcvConvArgs& a, Plan& pl) {
+// io: the IO bits of the instance that will run (its template argument)
+template <class EL>
+bool choose(const VcvConvArgs& a, Plan& pl, int io) {
   const int U = a.Q * a.P;
   if (U < 96) return false;
-  const int nph = a.phases > 1 ? a.phases : 1;
-  auto blocks = [&](int bm, int bn) { return (long long)a.B * vcv_cdiv(U, bn) * vcv_cdiv(a.Mg, bm) * nph; };
+  const int nph = conv_phases(a);
+  auto blocks = [&](int bm, int bn) { return conv_blocks(a, bm, bn); };
   bool ok = false;
-  // fill of the last round of 256 workgroups x useful columns of the position tiles
-  auto eff2 = [&](int bm, int bn) {
-    const long long nb = blocks(bm, bn);
-    const long long rounds = (nb + 255) / 256;
-    return ((double)U / ((double)vcv_cdiv(U, bn) * bn)) * ((double)nb / (double)(rounds * 256));
-  };
+  auto eff2 = [&](int bm, int bn) { return conv_round_fill(a, bm, bn); };
   if (a.Mg >= 128) {
     // (the 3-phase data gradients of the 512-channel period layers: 384 tiles of 128 rows run 1.5 rounds, 768 of 64 rows 3)
     if (U > 160 && U <= 224 && eff2(64, 224) > eff2(128, 224) + 0.2 && make_plan<EL>(a, 64, 224, 14, pl)) pl.variant = 6, ok = true;
@@ -440,11 +418,7 @@ bool choose(const VcvConvArgs& a, Plan& pl) {
       // tile width by efficiency = (useful columns of the position tiles) x (fill of the last round of 256 workgroups):
       // the 128 -> 512 period layers have 608-629 positions per batch element: 3 tiles of 256 waste a fifth of the
       // columns and 384 workgroups run 1.5 rounds (0.59), 2 tiles of 320 waste 3-5 % in exactly one round (0.95)
-      auto eff = [&](int bn) {
-        const long long nb = blocks(128, bn);
-        const long long rounds = (nb + 255) / 256;
-        return ((double)U / ((double)vcv_cdiv(U, bn) * bn)) * ((double)nb / (double)(rounds * 256));
-      };
+      auto eff = [&](int bn) { return conv_round_fill(a, 128, bn); };
       const double e256 = (U > 160 && blocks(128, 256) >= 256) ? eff(256) : 0.0, e128 = eff(128);
       const double e320 = (U > 320 && blocks(128, 320) >= 160) ? eff(320) : 0.0;
       if (e320 > e256 + 0.08 && e320 > e128 + 0.08 && make_plan<EL>(a, 128, 320, 8, pl)) pl.variant = 11, ok = true;
@@ -478,7 +452,7 @@ bool choose(const VcvConvArgs& a, Plan& pl) {
   // channels: 39 -> 36) and the bf16 launches with <= 64 input channels (278 -> 252 on the 64-channel k7 layers: two
   // workgroups per CU there, and the 32 staged floats per task cost registers) lose and keep dword loads
   const bool no_x4 = !vcv_tuning().pk_x4;
-  if (ok && (IO & 1)) {
+  if (ok && (io & 1)) {
     // bf16 activations: always 16-byte loads of eight positions (the only loader of a bf16 `x`)
     Plan p2;
     if (pl.variant == 12 || pl.variant == 13 || !make_plan<EL>(a, pl.BM, pl.BN, pl.NW, p2, 0, 8)) return false;
@@ -493,7 +467,7 @@ bool choose(const VcvConvArgs& a, Plan& pl) {
   // too few tiles for 256 CUs: split the reduction over ks blocks per tile (deterministic slabs + finishing pass),
   // aiming at one full round of resident workgroups (256 x the workgroups a CU holds at this LDS footprint)
   const long long nb = blocks(pl.BM, pl.BN);
-  if (IO == 0 && nph == 1 && nb < 192 && pl.g.nch >= 4) {  // (bf16 activations: no split -- the finishing passes are fp32-only)
+  if (io == 0 && nph == 1 && nb < 192 && pl.g.nch >= 4) {  // (bf16 activations: no split -- the finishing passes are fp32-only)
     // (bf16 chunks are short enough that the finishing pass outweighs a second resident round: measured, it keeps
     // the flat 384 target)
     const long long target = pl.lds_bytes * 2 <= VCV_LDS_LIMIT ? 512 : 256;
@@ -505,18 +479,17 @@ bool choose(const VcvConvArgs& a, Plan& pl) {
     }
   }
   // 16-byte epilogue through LDS: output rows contiguous in the column index, room for a 32 x 40 float tile per MFMA wave
-  const bool no_vec = !vcv_tuning().pk_vec;
-  pl.g.vec = (!no_vec && nph == 1 && a.os == 1 && a.oo == 0 && (!a.mask || a.P == 1) &&
-              (size_t)pl.NW * 32 * 40 * 4 <= pl.lds_bytes) ? 1 : 0;
+  pl.g.vec = conv_vec(a, pl.NW, pl.lds_bytes);
   // bf16 `y`: the 16-byte stores carry eight columns: rows of a multiple of eight elements, 16-byte aligned tensors
-  if ((IO & 2) && ((a.Tout * a.P) % 8 != 0 || (((uintptr_t)a.y | (uintptr_t)a.res) & 15))) pl.g.vec = 0;
+  if ((io & 2) && ((a.Tout * a.P) % 8 != 0 || (((uintptr_t)a.y | (uintptr_t)a.res) & 15))) pl.g.vec = 0;
   if (a.ms > 1) pl.g.vec = 0;  // (merged phases: the interleaving epilogue)
   return true;
 }
 
 template <class EL, int TM, int TN, int WM, int WN, int NP = 0, int IO = 0>
-int launch(const VcvConvArgs& a, const Plan& pl, typename EL::frag* wp, float* part, int flip, bool pack_valid, hipStream_t st) {
+int launch(const VcvConvArgs& a, const Plan& pl, typename EL::frag* wp, float* part, int flip, bool pack_valid, hipStream_t st, int32_t* desc) {
   constexpr int BM = 32 * TM * WM, NT = 64 * (WM * WN + NP);
+  if (desc) { desc[3] = NT; return VCV_OK; }  // vcv_conv_plan_describe: the instantiation this launch would run
   const BfGeom& g = pl.g;
   if (!pack_valid) {
     const size_t total = pl.pack_bytes / 16;
@@ -536,26 +509,10 @@ int launch(const VcvConvArgs& a, const Plan& pl, typename EL::frag* wp, float* p
                        : (a.in_tf == VCV_TF_LEAKY ? conv_pk_kernel<EL, TM, TN, WM, WN, true, (NP ? MAXT_WS : MAXT), NP, false>
                                                   : conv_pk_kernel<EL, TM, TN, WM, WN, false, (NP ? MAXT_WS : MAXT), NP, false>);
   }
-  if (pl.lds_bytes > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes) != hipSuccess)
-    return VCV_EHIP;
-  dim3 grid(a.B * g.ntu * g.ks, g.nmt, g.phases), block(NT);
-  const double flops = 2.0 * a.B * a.Mg * a.Cg * a.K * a.P * (double)(g.phases > 1 ? a.Tin : a.Q);
-  const int tag[12] = {a.B, EL::ESZ == 2 ? 2 : 4, a.Cg, a.Mg, a.K, a.Q, a.P, a.s, g.phases, a.a_mode + 10 * g.ks, BM * 1000 + pl.BN, g.BKC};
-  const double esz = IO ? 2.0 : 4.0;  // bytes per activation element in HBM
-  const double abytes = esz * (double)a.B * a.Cg * a.Tin * a.P + 4.0 * (double)a.Mg * a.Cg * a.K +
-                        esz * (double)a.B * (a.ms > 1 ? a.Mg / a.ms : a.Mg) * a.Tout * a.P * (1 + (a.res ? 1 : 0) + (a.oaux ? 1 : 0) + (a.accumulate ? 1 : 0));
-  hipEvent_t ev0, ev1;
-  vcv_prof_events(VCV_PROF_CONV_DMA, flops, tag, 12, &ev0, &ev1, abytes, EL::ESZ == 2 ? flops / VCV_PEAK_BF16_MFMA : 0.0);
-  VCV_LAUNCH_EV(kern, grid, block, (unsigned)pl.lds_bytes, st, ev0, ev1, a, g, (const typename EL::frag*)wp, part);
-  if (g.ks > 1) {
-    const size_t n = (size_t)a.B * a.Mg * a.Q * a.P;
-    if (g.vec && !a.mask && n % 4 == 0 && a.Q == a.Tout && a.Q * a.P >= 4)
-      hipLaunchKernelGGL(conv_pk_finish4_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, a, (const float*)part, g.ks);
-    else
-      hipLaunchKernelGGL(conv_pk_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, (const float*)part, g.ks);
-  }
-  return vcv_check_launch();
+  // (IO: 2 bytes per activation element in HBM)
+  return conv_launch_tail(kern, a, g, dim3(a.B * g.ntu * g.ks, g.nmt, g.phases), NT, pl.lds_bytes, st,
+                          {EL::ESZ == 2 ? 2 : 4, BM * 1000 + pl.BN, g.BKC}, conv_abytes(a, IO ? 2.0 : 4.0, true), EL::ESZ == 2 ? 1 : 0,
+                          (const typename EL::frag*)wp, part, conv_pk_finish_kernel, conv_pk_finish4_kernel, g.vec != 0);
 }
 
 // fp32: with 16-byte input loads this kernel is ahead of the LDS-DMA kernel (conv_dma.hip) on every shape of the step
@@ -570,7 +527,7 @@ template <class EL, int IO = 0>
 int plan_t(const VcvConvArgs* args, int flip, int64_t* out) {
   if (!args || !out || !eligible(*args, IO) || !wanted<EL>(*args)) return VCV_EINVAL;
   Plan pl;
-  if (!choose<EL, IO>(*args, pl)) return VCV_EINVAL;
+  if (!choose<EL>(*args, pl, IO)) return VCV_EINVAL;
   out[0] = (int64_t)((pl.pack_bytes + 3) / 4);
   out[1] = (int64_t)pl.scratch_floats;
   const BfGeom& g = pl.g;
@@ -580,53 +537,45 @@ int plan_t(const VcvConvArgs* args, int flip, int64_t* out) {
 }
 
 template <class EL, int IO = 0>
-int run_t(const VcvConvArgs* args, float* pack_ws, float* scratch_ws, int flip, int pack_valid, void* stream) {
-  if (!args || !pack_ws || !eligible(*args, IO) || !wanted<EL>(*args)) return VCV_EINVAL;
+int run_t(const VcvConvArgs* args, float* pack_ws, float* scratch_ws, int flip, int pack_valid, void* stream, int32_t* desc = nullptr) {
+  if (!args || (!pack_ws && !desc) || !eligible(*args, IO) || !wanted<EL>(*args)) return VCV_EINVAL;
   Plan pl;
-  if (!choose<EL, IO>(*args, pl)) return VCV_EINVAL;
-  if (pl.g.ks > 1 && !scratch_ws) return VCV_EINVAL;
+  if (!choose<EL>(*args, pl, IO)) return VCV_EINVAL;
+  if (pl.g.ks > 1 && !scratch_ws && !desc) return VCV_EINVAL;
+  if (desc) {
+    const BfGeom& g = pl.g;
+    const int32_t d[16] = {pl.variant, pl.BM, pl.BN, 0, g.BKC, g.JA, g.phases, g.nch, g.ks, g.vec, g.xcd, (int32_t)pl.lds_bytes,
+                           pl.ppl, g.nch > 1 ? 2 : 1, args->ms > 1 ? 1 : 0, g.xw};
+    for (int i = 0; i < 16; ++i) desc[i] = d[i];
+  }
   hipStream_t st = (hipStream_t)stream;
   typename EL::frag* wp = reinterpret_cast<typename EL::frag*>(pack_ws);
   const bool pv = pack_valid != 0;
-  if constexpr (IO != 0) {
-    switch (pl.variant) {
-      case 0: return launch<EL, 2, 2, 2, 4, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st);
-      case 1: return launch<EL, 2, 1, 2, 4, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st);
-      case 2: return launch<EL, 2, 1, 2, 7, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st);
-      case 3: return launch<EL, 1, 2, 2, 4, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st);
-      case 4: return launch<EL, 1, 1, 2, 4, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st);
-      case 5: return launch<EL, 1, 1, 1, 8, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st);
-      case 6: return launch<EL, 1, 1, 2, 7, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st);
-      case 8: return launch<EL, 1, 2, 1, 8, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st);
-      case 16: return launch<EL, 2, 1, 1, 9, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st);
-      case 11: return launch<EL, 1, 5, 4, 2, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st);
-      case 7: return launch<EL, 4, 1, 1, 9, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st);
-      default: return VCV_EINVAL;
-    }
-  } else {
   switch (pl.variant) {
-    case 0: return launch<EL, 2, 2, 2, 4>(*args, pl, wp, scratch_ws, flip, pv, st);
-    case 1: return launch<EL, 2, 1, 2, 4>(*args, pl, wp, scratch_ws, flip, pv, st);
-    case 2: return launch<EL, 2, 1, 2, 7>(*args, pl, wp, scratch_ws, flip, pv, st);
-    case 3: return launch<EL, 1, 2, 2, 4>(*args, pl, wp, scratch_ws, flip, pv, st);
-    case 4: return launch<EL, 1, 1, 2, 4>(*args, pl, wp, scratch_ws, flip, pv, st);
-    case 5: return launch<EL, 1, 1, 1, 8>(*args, pl, wp, scratch_ws, flip, pv, st);
-    case 6: return launch<EL, 1, 1, 2, 7>(*args, pl, wp, scratch_ws, flip, pv, st);
-    case 8: return launch<EL, 1, 2, 1, 8>(*args, pl, wp, scratch_ws, flip, pv, st);   // 32 x 512
-    case 16: return launch<EL, 2, 1, 1, 9>(*args, pl, wp, scratch_ws, flip, pv, st);  // 64 x 288, 9 waves of 64 rows x 32 columns
-    case 12: return launch<EL, 2, 2, 2, 4, 4>(*args, pl, wp, scratch_ws, flip, pv, st);  // 128 x 256, 8 MFMA + 4 producer waves
-    case 13: return launch<EL, 1, 7, 4, 1, 4>(*args, pl, wp, scratch_ws, flip, pv, st);  // 128 x 224, 4 MFMA waves of 32 x 224 + 4 producers
-    case 11: return launch<EL, 1, 5, 4, 2>(*args, pl, wp, scratch_ws, flip, pv, st);  // 128 x 320: 8 waves of 32 rows x 5 column tiles
-    default: return launch<EL, 4, 1, 1, 9>(*args, pl, wp, scratch_ws, flip, pv, st);
+    case 0: return launch<EL, 2, 2, 2, 4, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st, desc);
+    case 1: return launch<EL, 2, 1, 2, 4, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st, desc);
+    case 2: return launch<EL, 2, 1, 2, 7, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st, desc);
+    case 3: return launch<EL, 1, 2, 2, 4, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st, desc);
+    case 4: return launch<EL, 1, 1, 2, 4, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st, desc);
+    case 5: return launch<EL, 1, 1, 1, 8, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st, desc);
+    case 6: return launch<EL, 1, 1, 2, 7, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st, desc);
+    case 7: return launch<EL, 4, 1, 1, 9, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st, desc);
+    case 8: return launch<EL, 1, 2, 1, 8, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st, desc);   // 32 x 512
+    case 11: return launch<EL, 1, 5, 4, 2, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st, desc);  // 128 x 320: 8 waves of 32 rows x 5 column tiles
+    case 16: return launch<EL, 2, 1, 1, 9, 0, IO>(*args, pl, wp, scratch_ws, flip, pv, st, desc);  // 64 x 288, 9 waves of 64 rows x 32 columns
   }
+  if constexpr (IO == 0) {  // the producer-wave twins: fp32 activations only
+    if (pl.variant == 12) return launch<EL, 2, 2, 2, 4, 4>(*args, pl, wp, scratch_ws, flip, pv, st, desc);  // 128 x 256, 8 MFMA + 4 producer waves
+    if (pl.variant == 13) return launch<EL, 1, 7, 4, 1, 4>(*args, pl, wp, scratch_ws, flip, pv, st, desc);  // 128 x 224, 4 MFMA waves of 32 x 224 + 4 producers
   }
+  return VCV_EINVAL;
 }
 
 template <class EL>
 int pack_job_t(const VcvConvArgs* args, int flip, VcvPackJob* out) {
   if (!args || !out || !eligible(*args) || !wanted<EL>(*args)) return VCV_EINVAL;
   Plan pl;
-  if (!choose<EL>(*args, pl)) return VCV_EINVAL;
+  if (!choose<EL>(*args, pl, 0)) return VCV_EINVAL;
   const BfGeom& g = pl.g;
   out->kind = EL::ESZ == 2 ? 2 : 1;
   out->M = args->Mg, out->C = args->Cg, out->K = args->K;

@@ -37,6 +37,7 @@
 #include "common.h"
 #include "prof.h"
 #include "conv_tile.h"
+#include "conv_plan.h"
 
 namespace {
 
@@ -557,30 +558,16 @@ struct Plan {
   size_t scratch_floats, pack_bytes, lds_bytes;
 };
 
-bool eligible(const VcvConvArgs& a) {
-  const bool fwd_type = a.a_mode == 0 && a.phases <= 1;
-  const bool phased = a.a_mode == 1 && a.phases > 1 && a.s == 1 && a.dj == -1;
-  return (fwd_type || phased) && a.G == 1 && a.io == 0 && a.post_scale == 0.f && a.ms <= 1 &&
-         (a.in_tf == VCV_TF_NONE || (a.in_tf == VCV_TF_LEAKY && a.slope < 1.f && a.slope >= 0.f)) && a.Mg >= 32 &&
-         a.Cg >= 16 && a.K <= 16 && a.s >= 1 && a.s <= 3 && (long long)a.Tin * a.P * 4 < (1ll << 31) &&
-         (long long)a.Mg * a.Tout * a.P < (1ll << 31);
-}
+bool eligible(const VcvConvArgs& a) { return conv_eligible(a, true); }
 
 bool make_plan(const VcvConvArgs& a, int BM, int BN, int NW, Plan& pl, int nring = NRING_DEF, int js = 1) {
   pl.BM = BM; pl.BN = BN; pl.NW = NW;
   pl.merged = 0; pl.nring = nring;
   BfGeom& g = pl.g;
-  const int qspan = (BN - 1) / a.P + 1;
-  const int adj = a.dj < 0 ? -a.dj : a.dj;
-  g.phases = a.phases > 1 ? a.phases : 1;
-  g.JA = vcv_cdiv(a.K, g.phases);
-  const int rowmax = (qspan * a.s + (g.JA - 1) * adj + 1) * a.P;
-  g.xw = (rowmax + 3 + 63) & ~63;  // (up to three floats of round-down at the start)
+  conv_span(a, BM, BN, 3, g);  // (up to three floats of round-down at the start)
   g.BKC = 16;
   g.ncg = 1;
   g.nch = vcv_cdiv(a.Cg, 16);
-  g.ntu = vcv_cdiv(a.Q * a.P, BN);
-  g.nmt = vcv_cdiv(a.Mg, BM);
   g.a_bytes = js * 3 * 2 * BM * 16;  // the weight slab of a stage (js taps)
   pl.js = js;
   g.buf_bytes = 3 * 2 * g.xw * 16;
@@ -588,10 +575,7 @@ bool make_plan(const VcvConvArgs& a, int BM, int BN, int NW, Plan& pl, int nring
   if (pl.lds_bytes > VCV_LDS_LIMIT) return false;
   g.ks = 1;
   g.vec = 0;
-  const int xcd_remap = vcv_tuning().xcd_remap;
-  // nothing to share when a column tile has one workgroup (measured: the re-deal alone costs the 64 x 10 s decode 11 %:
-  // eight XCDs walking eight far-apart regions of the tensor instead of one)
-  g.xcd = xcd_remap && g.nmt * (g.phases > 1 ? g.phases : 1) > 1;
+  g.xcd = conv_xcd(g.nmt * g.phases);
   pl.pack_bytes = (size_t)g.phases * g.nmt * g.nch * g.JA * (3 * 2 * BM * 16);
   pl.scratch_floats = 0;
   return true;
@@ -608,7 +592,7 @@ bool make_plan_merged(const VcvConvArgs& a, int BM, int BN, int variant, Plan& p
   if (nring < 2) return false;
   pl.lds_bytes = (size_t)nring * g.a_bytes + 2ull * g.buf_bytes;
   pl.merged = 1, pl.nring = nring, pl.variant = variant;
-  g.xcd = vcv_tuning().xcd_remap && g.nmt > 1;  // (the workgroups sharing a span are the m-tiles alone)
+  g.xcd = conv_xcd(g.nmt);  // (the workgroups sharing a span are the m-tiles alone)
   return true;
 }
 
@@ -626,20 +610,17 @@ bool choose(const VcvConvArgs& a, Plan& pl) {
     static const int VBM[7] = {128, 128, 256, 64, 64, 32, 64}, VBN[7] = {256, 128, 128, 256, 128, 256, 512};
     const int v = g_force_variant;
     if (v > 6 || a.Mg < (v == 5 ? 32 : VBM[v] / 2 + 1)) return false;
-    const int js = (g_force_js == 2 && (v == 0 || v == 1) && vcv_cdiv(a.K, a.phases > 1 ? a.phases : 1) >= 2) ? 2 : 1;
+    const int js = (g_force_js == 2 && (v == 0 || v == 1) && vcv_cdiv(a.K, conv_phases(a)) >= 2) ? 2 : 1;
     if (!make_plan(a, VBM[v], VBN[v], 8, pl, v == 2 ? 2 : NRING_DEF, js)) return false;
     pl.variant = v;
-    const int nph0 = a.phases > 1 ? a.phases : 1;
-    if (g_force_ks >= 2 && nph0 == 1 && pl.g.nch >= 2 * g_force_ks) {
+    if (g_force_ks >= 2 && conv_phases(a) == 1 && pl.g.nch >= 2 * g_force_ks) {
       pl.g.ks = g_force_ks;
       pl.scratch_floats = (size_t)g_force_ks * a.B * a.Mg * U;
     }
-    const bool no_vec0 = !vcv_tuning().pk_vec;
-    pl.g.vec = (!no_vec0 && nph0 == 1 && a.os == 1 && a.oo == 0 && (!a.mask || a.P == 1) &&
-                (size_t)pl.NW * 32 * 40 * 4 <= pl.lds_bytes) ? 1 : 0;
+    pl.g.vec = conv_vec(a, pl.NW, pl.lds_bytes);
     return true;
   }
-  const int nph = a.phases > 1 ? a.phases : 1;
+  const int nph = conv_phases(a);
   // Phased launches of 2 or 3 residues: one workgroup per (column tile, m-tile) computes every residue from one staged span
   // (conv_x3_merged_kernel).  Three accumulator sets fit the register file for 2 x 1, 1 x 2 and 1 x 1 wave tiles, so the rows
   // follow Mg as below and the columns are what those wave tiles leave.  The merged grid is 1 / phases of the per-residue one
@@ -650,13 +631,8 @@ bool choose(const VcvConvArgs& a, Plan& pl) {
     const long long nbm = (long long)a.B * vcv_cdiv(U, bn) * vcv_cdiv(a.Mg, bm);
     if ((g_all || nbm * nph > 256) && make_plan_merged(a, bm, bn, bm == 128 ? 1 : bm == 64 ? 3 : 5, pl)) return true;
   }
-  auto blocks = [&](int bm, int bn) { return (long long)a.B * vcv_cdiv(U, bn) * vcv_cdiv(a.Mg, bm) * nph; };
-  auto eff = [&](int bm, int bn) {
-    const long long nb = blocks(bm, bn);
-    const long long rounds = (nb + 255) / 256;
-    return ((double)U / ((double)vcv_cdiv(U, bn) * bn)) * ((double)a.Mg / ((double)vcv_cdiv(a.Mg, bm) * bm)) *
-           ((double)nb / (double)(rounds * 256));
-  };
+  auto blocks = [&](int bm, int bn) { return conv_blocks(a, bm, bn); };
+  auto eff = [&](int bm, int bn) { return conv_round_fill_rows(a, bm, bn); };
   bool ok = false;
   if (a.Mg >= 96) {
     const double e256 = U > 160 ? eff(128, 256) : 0.0, e128 = eff(128, 128);
@@ -704,9 +680,7 @@ bool choose(const VcvConvArgs& a, Plan& pl) {
       pl.scratch_floats = (size_t)ks * a.B * a.Mg * U;
     }
   }
-  const bool no_vec = !vcv_tuning().pk_vec;
-  pl.g.vec = (!no_vec && nph == 1 && a.os == 1 && a.oo == 0 && (!a.mask || a.P == 1) &&
-              (size_t)pl.NW * 32 * 40 * 4 <= pl.lds_bytes) ? 1 : 0;
+  pl.g.vec = conv_vec(a, pl.NW, pl.lds_bytes);
   return true;
 }
 
@@ -715,9 +689,12 @@ bool choose(const VcvConvArgs& a, Plan& pl) {
 // output scale -- the error of the fp32 accumulation order, as large for the fp32-input MFMA kernel -- because each left
 // out term is below 2^-24 of its product while one accumulator rounding is 2^-24 of the whole running sum.
 
-template <int NTERM, int TM, int TN, int WM, int WN, int NRING = NRING_DEF, int JS = 1>
-int launch(const VcvConvArgs& a, const Plan& pl, char* wp, float* part, int flip, bool pack_valid, hipStream_t st) {
-  constexpr int BM = 32 * TM * WM, NT = 64 * (WM * WN + NPROD);
+// The weight pack (unless the caller's is valid) and the launch of `kern` (BM rows per tile, NT threads) over the plan's grid;
+// last: the partial-sum slabs of a split launch, or the merged-phase kernel's ring depth (its grid has no phase dimension).
+template <int NTERM, int BM, int NT, class Kern, class Last>
+int pack_and_launch(Kern kern, const VcvConvArgs& a, const Plan& pl, char* wp, Last last, int flip, bool pack_valid, hipStream_t st,
+                    int32_t* desc) {
+  if (desc) { desc[3] = NT; return VCV_OK; }  // vcv_conv_plan_describe: the instantiation this launch would run
   const BfGeom& g = pl.g;
   if (!pack_valid) {
     const size_t total = (size_t)g.phases * g.nmt * g.nch * g.JA * 2 * BM;
@@ -725,77 +702,48 @@ int launch(const VcvConvArgs& a, const Plan& pl, char* wp, float* part, int flip
     hipLaunchKernelGGL(pack_x3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.w, (bf16x8*)wp, a.Mg, a.Cg,
                        a.K, BM, g.JA, g.nch, g.nmt, g.phases, mode, total);
   }
+  // (a merged launch carries the profiler tag and flop count of the per-residue launch: one launch, counted once)
+  return conv_launch_tail(kern, a, g, dim3(a.B * g.ntu * g.ks, g.nmt, pl.merged ? 1 : g.phases), NT, pl.lds_bytes, st,
+                          {3, BM * 1000 + pl.BN, NTERM}, conv_abytes(a, 4.0, false), NTERM, (const char*)wp, last,
+                          conv_pk_finish_kernel, conv_pk_finish4_kernel, g.vec != 0);
+}
+
+template <int NTERM, int TM, int TN, int WM, int WN, int NRING = NRING_DEF, int JS = 1>
+int launch(const VcvConvArgs& a, const Plan& pl, char* wp, float* part, int flip, bool pack_valid, hipStream_t st, int32_t* desc) {
   void (*kern)(const VcvConvArgs, const BfGeom, const char*, float*) =
       a.in_tf == VCV_TF_LEAKY ? conv_x3_kernel<NTERM, TM, TN, WM, WN, true, NRING, JS> : conv_x3_kernel<NTERM, TM, TN, WM, WN, false, NRING, JS>;
-  if (pl.lds_bytes > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes) != hipSuccess)
-    return VCV_EHIP;
-  dim3 grid(a.B * g.ntu * g.ks, g.nmt, g.phases), block(NT);
-  const double flops = 2.0 * a.B * a.Mg * a.Cg * a.K * a.P * (double)(g.phases > 1 ? a.Tin : a.Q);
-  const int tag[12] = {a.B, 3, a.Cg, a.Mg, a.K, a.Q, a.P, a.s, g.phases, a.a_mode + 10 * g.ks, BM * 1000 + pl.BN, NTERM};
-  const double abytes = 4.0 * ((double)a.B * a.Cg * a.Tin * a.P + (double)a.Mg * a.Cg * a.K +
-                               (double)a.B * a.Mg * a.Tout * a.P * (1 + (a.res ? 1 : 0) + (a.oaux ? 1 : 0)));
-  hipEvent_t ev0, ev1;
-  vcv_prof_events(VCV_PROF_CONV_DMA, flops, tag, 12, &ev0, &ev1, abytes, NTERM * flops / VCV_PEAK_BF16_MFMA);
-  VCV_LAUNCH_EV(kern, grid, block, (unsigned)pl.lds_bytes, st, ev0, ev1, a, g, (const char*)wp, part);
-  if (g.ks > 1) {
-    const size_t n = (size_t)a.B * a.Mg * a.Q * a.P;
-    if (g.vec && !a.mask && n % 4 == 0 && a.Q == a.Tout && a.Q * a.P >= 4)
-      hipLaunchKernelGGL(conv_pk_finish4_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, a, (const float*)part, g.ks);
-    else
-      hipLaunchKernelGGL(conv_pk_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, (const float*)part, g.ks);
-  }
-  return vcv_check_launch();
+  return pack_and_launch<NTERM, 32 * TM * WM, 64 * (WM * WN + NPROD)>(kern, a, pl, wp, part, flip, pack_valid, st, desc);
 }
 
 template <int NTERM, int PH, int TM, int TN, int WM, int WN>
-int launch_merged(const VcvConvArgs& a, const Plan& pl, char* wp, int flip, bool pack_valid, hipStream_t st) {
-  constexpr int BM = 32 * TM * WM, NT = 64 * (WM * WN + NPROD);
-  const BfGeom& g = pl.g;
-  if (!pack_valid) {
-    const size_t total = (size_t)g.phases * g.nmt * g.nch * g.JA * 2 * BM;
-    hipLaunchKernelGGL(pack_x3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.w, (bf16x8*)wp, a.Mg, a.Cg,
-                       a.K, BM, g.JA, g.nch, g.nmt, g.phases, 2, total);
-  }
+int launch_merged(const VcvConvArgs& a, const Plan& pl, char* wp, int flip, bool pack_valid, hipStream_t st, int32_t* desc) {
   void (*kern)(const VcvConvArgs, const BfGeom, const char*, int) =
       a.in_tf == VCV_TF_LEAKY ? conv_x3_merged_kernel<NTERM, PH, TM, TN, WM, WN, true> : conv_x3_merged_kernel<NTERM, PH, TM, TN, WM, WN, false>;
-  if (pl.lds_bytes > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes) != hipSuccess)
-    return VCV_EHIP;
-  dim3 grid(a.B * g.ntu, g.nmt, 1), block(NT);
-  // (profiler tag and flop count of the per-residue launch: one launch, counted once)
-  const double flops = 2.0 * a.B * a.Mg * a.Cg * a.K * a.P * (double)a.Tin;
-  const int tag[12] = {a.B, 3, a.Cg, a.Mg, a.K, a.Q, a.P, a.s, g.phases, a.a_mode + 10 * g.ks, BM * 1000 + pl.BN, NTERM};
-  const double abytes = 4.0 * ((double)a.B * a.Cg * a.Tin * a.P + (double)a.Mg * a.Cg * a.K +
-                               (double)a.B * a.Mg * a.Tout * a.P * (1 + (a.res ? 1 : 0) + (a.oaux ? 1 : 0)));
-  hipEvent_t ev0, ev1;
-  vcv_prof_events(VCV_PROF_CONV_DMA, flops, tag, 12, &ev0, &ev1, abytes, NTERM * flops / VCV_PEAK_BF16_MFMA);
-  VCV_LAUNCH_EV(kern, grid, block, (unsigned)pl.lds_bytes, st, ev0, ev1, a, g, (const char*)wp, pl.nring);
-  return vcv_check_launch();
+  return pack_and_launch<NTERM, 32 * TM * WM, 64 * (WM * WN + NPROD)>(kern, a, pl, wp, pl.nring, flip, pack_valid, st, desc);
 }
 
 template <int NTERM, int PH>
-int run_merged(const VcvConvArgs& a, const Plan& pl, char* wp, int flip, bool pv, hipStream_t st) {
+int run_merged(const VcvConvArgs& a, const Plan& pl, char* wp, int flip, bool pv, hipStream_t st, int32_t* desc) {
   switch (pl.variant) {
-    case 1: return launch_merged<NTERM, PH, 2, 1, 2, 4>(a, pl, wp, flip, pv, st);  // 128 x 128
-    case 3: return launch_merged<NTERM, PH, 1, 2, 2, 4>(a, pl, wp, flip, pv, st);  // 64 x 256
-    default: return launch_merged<NTERM, PH, 1, 1, 1, 8>(a, pl, wp, flip, pv, st);  // 32 x 256
+    case 1: return launch_merged<NTERM, PH, 2, 1, 2, 4>(a, pl, wp, flip, pv, st, desc);  // 128 x 128
+    case 3: return launch_merged<NTERM, PH, 1, 2, 2, 4>(a, pl, wp, flip, pv, st, desc);  // 64 x 256
+    default: return launch_merged<NTERM, PH, 1, 1, 1, 8>(a, pl, wp, flip, pv, st, desc);  // 32 x 256
   }
 }
 
 template <int NTERM>
-int run_n(const VcvConvArgs& a, const Plan& pl, char* wp, float* part, int flip, bool pv, hipStream_t st) {
-  if (pl.merged) return pl.g.phases == 2 ? run_merged<NTERM, 2>(a, pl, wp, flip, pv, st) : run_merged<NTERM, 3>(a, pl, wp, flip, pv, st);
+int run_n(const VcvConvArgs& a, const Plan& pl, char* wp, float* part, int flip, bool pv, hipStream_t st, int32_t* desc) {
+  if (pl.merged) return pl.g.phases == 2 ? run_merged<NTERM, 2>(a, pl, wp, flip, pv, st, desc) : run_merged<NTERM, 3>(a, pl, wp, flip, pv, st, desc);
   switch (pl.variant) {
-    case 0: return pl.js == 2 ? launch<NTERM, 2, 2, 2, 4, NRING_DEF, 2>(a, pl, wp, part, flip, pv, st)
-                              : launch<NTERM, 2, 2, 2, 4>(a, pl, wp, part, flip, pv, st);
-    case 1: return pl.js == 2 ? launch<NTERM, 2, 1, 2, 4, NRING_DEF, 2>(a, pl, wp, part, flip, pv, st)
-                              : launch<NTERM, 2, 1, 2, 4>(a, pl, wp, part, flip, pv, st);
-    case 2: return launch<NTERM, 2, 2, 4, 2, 2>(a, pl, wp, part, flip, pv, st);  // 256 x 128
-    case 3: return launch<NTERM, 1, 2, 2, 4>(a, pl, wp, part, flip, pv, st);
-    case 4: return launch<NTERM, 1, 1, 2, 4>(a, pl, wp, part, flip, pv, st);
-    case 6: return launch<NTERM, 1, 4, 2, 4>(a, pl, wp, part, flip, pv, st);  // 64 x 512
-    default: return launch<NTERM, 1, 1, 1, 8>(a, pl, wp, part, flip, pv, st);
+    case 0: return pl.js == 2 ? launch<NTERM, 2, 2, 2, 4, NRING_DEF, 2>(a, pl, wp, part, flip, pv, st, desc)
+                              : launch<NTERM, 2, 2, 2, 4>(a, pl, wp, part, flip, pv, st, desc);
+    case 1: return pl.js == 2 ? launch<NTERM, 2, 1, 2, 4, NRING_DEF, 2>(a, pl, wp, part, flip, pv, st, desc)
+                              : launch<NTERM, 2, 1, 2, 4>(a, pl, wp, part, flip, pv, st, desc);
+    case 2: return launch<NTERM, 2, 2, 4, 2, 2>(a, pl, wp, part, flip, pv, st, desc);  // 256 x 128
+    case 3: return launch<NTERM, 1, 2, 2, 4>(a, pl, wp, part, flip, pv, st, desc);
+    case 4: return launch<NTERM, 1, 1, 2, 4>(a, pl, wp, part, flip, pv, st, desc);
+    case 6: return launch<NTERM, 1, 4, 2, 4>(a, pl, wp, part, flip, pv, st, desc);  // 64 x 512
+    default: return launch<NTERM, 1, 1, 1, 8>(a, pl, wp, part, flip, pv, st, desc);
   }
 }
 
@@ -858,14 +806,29 @@ extern "C" int vcv_conv_x3_pack_job(const VcvConvArgs* args, int flip, VcvPackJo
   return VCV_OK;
 }
 
-extern "C" int vcv_conv_x3_run(const VcvConvArgs* args, float* pack_ws, float* scratch_ws, int flip, int pack_valid, void* stream) {
-  if (!args || !pack_ws || !eligible(*args) || !wanted(*args)) return VCV_EINVAL;
+static int run(const VcvConvArgs* args, float* pack_ws, float* scratch_ws, int flip, int pack_valid, void* stream, int32_t* desc) {
+  if (!args || (!pack_ws && !desc) || !eligible(*args) || !wanted(*args)) return VCV_EINVAL;
   Plan pl;
   if (!choose(*args, pl)) return VCV_EINVAL;
-  if (pl.g.ks > 1 && !scratch_ws) return VCV_EINVAL;
+  if (pl.g.ks > 1 && !scratch_ws && !desc) return VCV_EINVAL;
+  if (desc) {
+    const BfGeom& g = pl.g;
+    const int32_t d[16] = {pl.variant, pl.BM, pl.BN, 0, g.BKC, g.JA, g.phases, g.nch, g.ks, g.vec, g.xcd, (int32_t)pl.lds_bytes,
+                           pl.js, pl.nring, pl.merged, g.xw};
+    for (int i = 0; i < 16; ++i) desc[i] = d[i];
+  }
   hipStream_t st = (hipStream_t)stream;
-  return g_terms == 6 ? run_n<6>(*args, pl, (char*)pack_ws, scratch_ws, flip, pack_valid != 0, st)
-                      : run_n<9>(*args, pl, (char*)pack_ws, scratch_ws, flip, pack_valid != 0, st);
+  return g_terms == 6 ? run_n<6>(*args, pl, (char*)pack_ws, scratch_ws, flip, pack_valid != 0, st, desc)
+                      : run_n<9>(*args, pl, (char*)pack_ws, scratch_ws, flip, pack_valid != 0, st, desc);
+}
+
+extern "C" int vcv_conv_x3_run(const VcvConvArgs* args, float* pack_ws, float* scratch_ws, int flip, int pack_valid, void* stream) {
+  return run(args, pack_ws, scratch_ws, flip, pack_valid, stream, nullptr);
+}
+
+// vcv_conv_plan_describe, family 3
+extern "C" __attribute__((visibility("hidden"))) int vcv_conv_describe_x3(const VcvConvArgs* args, int flip, int32_t* out16) {
+  return run(args, nullptr, nullptr, flip, 1, nullptr, out16);
 }
 
 #ifdef VCV_X3_STAMPS

@@ -9,78 +9,42 @@ import torch
 
 from .._lib import (ACT_LEAKY, ACT_NONE, ACT_TANH, TF_DLEAKY, TF_LEAKY, TF_NONE, VcvConvArgs, VcvWgradArgs, check,
                     lib, ptr, stream)
-from .core import (LAUNCH_COUNTS, _ACT_TO_DTF, _COMPUTE, _DETERMINISTIC, _FAMILIES, _FAMILY_KEY, _GROUPED_BF16,
-                   _USE_DMA, _USE_PK, _USE_X3, _USE_X3_WGRAD, _cur_dev, _f32c, _rows, _sink, _sunk, conv_out_len)
-from .weights import (_PACK_JOBS, _stable_entry)
+from .core import (LAUNCH_COUNTS, _ACT_TO_DTF, _COMPUTE, _DETERMINISTIC, _GROUPED_BF16, _USE_DMA, _USE_X3, _USE_X3_WGRAD,
+                   _cur_dev, _f32c, _rows, _sink, _sunk, conv_out_len, live_families)
+from .weights import _packed_weights
 from .. import tuning
 
 
 def _launch_conv(a, flip_w=None, wt=None):
-    """Forward-type launches go to the packed-weight kernels when one is eligible -- the bf16-operand kernel
-    (vcv_conv_bf16_*) under set_compute_dtype("bf16"), else the fp32 LDS-DMA kernel (vcv_conv_dma_*) -- everything else to
-    the register-staged fp32 kernel.  flip_w: original [C, M, K] weight of a stride-1 data gradient (the pack flips it;
-    the register path needs the explicit flipped copy in a.w).  Packed weights of tensors inside a cached weight-norm
-    buffer (see _WeightNormManyFn) are kept with that buffer and reused until its parameters change."""
+    """A launch goes to the first packed-weight kernel family that takes it (core.live_families: the bf16-operand or the
+    split-operand kernel, the packed fp32 kernel, the LDS-DMA kernel), else to the register-staged fp32 kernel.  flip_w: the
+    original [C, M, K] weight of a stride-1 data gradient, in place of a.w (the families' packs flip it; the register kernel
+    gets an explicit flipped copy).  Packed weights of tensors inside a cached weight-norm buffer or a parameter region are
+    kept with it and reused until its parameters change (weights._packed_weights; wt: the weight tensor, for its version)."""
+    flip = 0
+    if flip_w is not None:
+        a.w, flip = ptr(flip_w), 1
     if _USE_DMA[0] and (a.a_mode == 0 or (a.a_mode == 1 and (a.phases > 1 or a.ms > 1))):
-        L = lib()
-        if flip_w is not None:
-            saved = a.w
-            a.w = ptr(flip_w)
-        flip = 1 if flip_w is not None else 0
         plan = (ctypes.c_int64 * 3)()
-        fkey = (_COMPUTE[0], _USE_X3[0], _USE_PK[0], a.io)
-        families = _FAMILIES.get(fkey)
-        if families is None and a.io != 0:  # bf16 activations: one family reads / writes them
-            families = _FAMILIES[fkey] = ((L.vcv_conv_bf16io_plan, L.vcv_conv_bf16io_run, "vcv_conv_bf16io_run"),)
-        if families is None:  # (built once per switch setting: this function runs ~450 times per step)
-            families = ((L.vcv_conv_bf16_plan, L.vcv_conv_bf16_run, "vcv_conv_bf16_run"),) if _COMPUTE[0] == "bf16" else ()
-            if _USE_X3[0] and _COMPUTE[0] == "f32":
-                families += ((L.vcv_conv_x3_plan, L.vcv_conv_x3_run, "vcv_conv_x3_run"),)
-            if _USE_PK[0]:
-                families += ((L.vcv_conv_pk_plan, L.vcv_conv_pk_run, "vcv_conv_pk_run"),)
-            families += ((L.vcv_conv_dma_plan, L.vcv_conv_dma_run, "vcv_conv_dma_run"),)
-            _FAMILIES[fkey] = families
-        for plan_fn, run_fn, name in families:
-            if plan_fn(ctypes.byref(a), flip, plan) != 0:
+        for fam in live_families(a.io):
+            if fam.plan(ctypes.byref(a), flip, plan) != 0:
                 continue
             dev = _cur_dev()
-            ent = _stable_entry(a.w)
-            wver = 0
-            if ent is not None and "dirty" in ent:
-                # a parameter region: the pack is valid for the weight tensor's version it was made from (an in-place write
-                # that did not go through the optimizer bumps it); callers that do not hand the tensor over pack per use
-                wtt = wt if wt is not None else flip_w
-                if wtt is None:
-                    ent = None
-                else:
-                    wver = wtt._version
-            packs = ent["packs"] if ent is not None else None
-            key = (a.w, plan[0], plan[2]) if wver == 0 else (a.w, plan[0], plan[2], wver)
-            pack = packs.get(key) if packs is not None else None
-            valid = 1 if pack is not None else 0
-            if pack is None:
-                pack = torch.empty((plan[0],), device=dev, dtype=torch.float32)
-                if packs is not None:
-                    packs[key] = pack
-                    # remember the job: the next time this tree's weights are re-normalised all of its packs are made
-                    # in one launch (_replay_packs)
-                    if len(_PACK_JOBS) > 64:
-                        _PACK_JOBS.clear()
-                    jobs = _PACK_JOBS.get(ent["key"])
-                    if jobs is None or jobs["shapes"] != ent["shapes"]:  # (a recycled address set is another module's)
-                        jobs = _PACK_JOBS[ent["key"]] = {"shapes": ent["shapes"], "jobs": {}}
-                    # (a region's job remembers the tensor version it was recorded at: the optimizer's raw update leaves
-                    # versions alone, so the replay registers the pack under the version the next use will ask for)
-                    jobs["jobs"][(a.w - ent["lo"], int(plan[0]), int(plan[2]), name)] = (bytes(a), flip, wver)
+            pack, valid = _packed_weights(a, flip, plan, fam, wt if wt is not None else flip_w, dev)
             scratch = torch.empty((plan[1],), device=dev, dtype=torch.float32) if plan[1] > 0 else None
-            check(run_fn(ctypes.byref(a), ptr(pack), ptr(scratch), flip, valid, stream()), name)
-            LAUNCH_COUNTS[_FAMILY_KEY.get(name, "dma")] += 1
+            check(fam.run(ctypes.byref(a), ptr(pack), ptr(scratch), flip, valid, stream()), fam.run_name)
+            LAUNCH_COUNTS[fam.name] += 1
             return
-        if flip_w is not None:
-            a.w = saved
     if a.io != 0:
         raise RuntimeError("vcvits_amd: no kernel takes this launch with bf16 activations (shape outside vcv_conv_bf16io_*)")
-    LAUNCH_COUNTS["gemm"] += 1
+    if flip_w is not None:
+        # no family takes the data gradient: the register kernel reads an explicit flipped / transposed copy, [a.Mg = C, a.Cg = M, K]
+        # (LAUNCH_COUNTS["gemm"] counts the launches that use their weights as they are)
+        wf = torch.empty((a.Mg, a.Cg, a.K), device=_cur_dev(), dtype=torch.float32)
+        check(lib().vcv_weight_flip_transpose(ptr(flip_w), ptr(wf), a.Cg, a.Mg, a.K, stream()), "vcv_weight_flip_transpose")
+        a.w = ptr(wf)
+    else:
+        LAUNCH_COUNTS["gemm"] += 1
     check(lib().vcv_conv_gemm(ctypes.byref(a), stream()), "vcv_conv_gemm")
 
 
@@ -104,6 +68,24 @@ def _launch_wgrad(a):
             return
     LAUNCH_COUNTS["wgrad"] += 1
     check(lib().vcv_conv_wgrad(ctypes.byref(a), stream()), "vcv_conv_wgrad")
+
+
+def _grouped41(which, groups, M, Cg, K, stride, pad, dil, P):
+    """Entry point of the grouped k = 41, stride 4 layers of DiscriminatorS (4 input channels per group, 4 or 16 output channels)
+    for which = "fwd" / "dgrad" / "wgrad", None for any other shape.  bf16 mode: the 16-channel groups on the bf16 matrix pipe
+    (4 taps x 4 channels per MFMA step)."""
+    if not (groups > 1 and Cg == 4 and K == 41 and stride == 4 and pad == 20 and dil == 1 and P == 1 and M // groups in (4, 16)):
+        return None
+    bf16 = _COMPUTE[0] == "bf16" and M // groups == 16 and _GROUPED_BF16[0]
+    return "vcv_grouped41_%s%s" % (which, "_bf16" if bf16 else "")
+
+
+def _phased(a, stride, pad, length, phases=None):
+    """The geometry of a strided transposed launch (ConvTranspose forward / strided data gradient) that writes `length` rows:
+    output row q * stride + r - pad for residue r, one launch phase per residue (phases=1: the residues are rows of the
+    launch, VcvConvArgs.ms)."""
+    a.s, a.dj, a.off, a.os, a.oo, a.phases = 1, -1, 0, stride, -pad, stride if phases is None else phases
+    a.Q = (length - 1 + pad) // stride + 1
 
 
 def _common(a, *, in_tf=TF_NONE, xaux=None, out_act=ACT_NONE, out_tf=TF_NONE, oaux=None, res=None,
@@ -131,11 +113,8 @@ def conv_forward(x, w, bias=None, stride=1, pad=0, dil=1, groups=1, out=None, **
         out = torch.empty(shape, device=x.device, dtype=torch.float32)
     plain = (all(kw.get(k) is None for k in ("res", "mask", "xaux", "oaux")) and not kw.get("accumulate", False)
              and kw.get("out_tf", TF_NONE) == TF_NONE and kw.get("alpha", 1.0) == 1.0)
-    if (groups > 1 and Cg == 4 and K == 41 and stride == 4 and pad == 20 and dil == 1 and P == 1
-            and M // groups in (4, 16) and plain and kw.get("in_tf", TF_NONE) == TF_NONE
-            and kw.get("out_act", ACT_NONE) in (ACT_NONE, ACT_LEAKY)):
-        # bf16 mode: the 16-channel groups on the bf16 matrix pipe (4 taps x 4 channels per MFMA step)
-        fn = "vcv_grouped41_fwd_bf16" if (_COMPUTE[0] == "bf16" and M // groups == 16 and _GROUPED_BF16[0]) else "vcv_grouped41_fwd"
+    fn = _grouped41("fwd", groups, M, Cg, K, stride, pad, dil, P)
+    if (fn and plain and kw.get("in_tf", TF_NONE) == TF_NONE and kw.get("out_act", ACT_NONE) in (ACT_NONE, ACT_LEAKY)):
         check(getattr(lib(), fn)(ptr(x), ptr(w), ptr(bias), ptr(out), B, groups, M // groups, Tin, Tout,
                                  kw.get("out_act", ACT_NONE), kw.get("slope", 0.1), stream()), fn)
         return out
@@ -173,10 +152,8 @@ def conv_dgrad(dy, w, x_shape, stride=1, pad=0, dil=1, groups=1, out=None, **kw)
     Cg, K = w.shape[1], w.shape[2]
     if out is None:
         out = torch.empty(tuple(x_shape), device=dy.device, dtype=torch.float32)
-    if (groups > 1 and Cg == 4 and K == 41 and stride == 4 and pad == 20 and dil == 1 and P == 1
-            and M // groups in (4, 16) and set(kw) <= {"in_tf", "xaux", "slope"}
-            and kw.get("in_tf", TF_NONE) in (TF_NONE, TF_DLEAKY)):
-        fn = "vcv_grouped41_dgrad_bf16" if (_COMPUTE[0] == "bf16" and M // groups == 16 and _GROUPED_BF16[0]) else "vcv_grouped41_dgrad"
+    fn = _grouped41("dgrad", groups, M, Cg, K, stride, pad, dil, P)
+    if fn and set(kw) <= {"in_tf", "xaux", "slope"} and kw.get("in_tf", TF_NONE) in (TF_NONE, TF_DLEAKY):
         check(getattr(lib(), fn)(ptr(dy), ptr(kw.get("xaux")), ptr(w), ptr(out), B, groups, M // groups, Tin,
                                  Tout, kw.get("in_tf", TF_NONE), kw.get("slope", 0.1), stream()), fn)
         return out
@@ -206,17 +183,7 @@ def conv_dgrad(dy, w, x_shape, stride=1, pad=0, dil=1, groups=1, out=None, **kw)
         a.Tin, a.Tout, a.P, a.K = Tout, Tin, P, K
         a.s, a.dj, a.off, a.os, a.oo, a.phases, a.Q, a.a_mode = 1, dil, pad - (K - 1) * dil, 1, 0, 1, Tin, 0
         _common(a, **kw)
-        a.w = ptr(w)
-        if _USE_DMA[0] and ((_COMPUTE[0] == "bf16" and lib().vcv_conv_bf16_plan(ctypes.byref(a), 1, (ctypes.c_int64 * 3)()) == 0)
-                            or (_COMPUTE[0] == "f32" and _USE_X3[0] and lib().vcv_conv_x3_plan(ctypes.byref(a), 1, (ctypes.c_int64 * 3)()) == 0)
-                            or (_USE_PK[0] and lib().vcv_conv_pk_plan(ctypes.byref(a), 1, (ctypes.c_int64 * 3)()) == 0)
-                            or lib().vcv_conv_dma_plan(ctypes.byref(a), 1, (ctypes.c_int64 * 3)()) == 0):
-            _launch_conv(a, flip_w=w)
-            return out
-        wt = torch.empty((C, M, K), device=dy.device, dtype=torch.float32)
-        check(lib().vcv_weight_flip_transpose(ptr(w), ptr(wt), M, C, K, stream()), "vcv_weight_flip_transpose")
-        a.w = ptr(wt)
-        check(lib().vcv_conv_gemm(ctypes.byref(a), stream()), "vcv_conv_gemm")
+        _launch_conv(a, flip_w=w)
         return out
     a = VcvConvArgs()
     a.x, a.w, a.y = ptr(dy), ptr(w), ptr(out)
@@ -228,8 +195,7 @@ def conv_dgrad(dy, w, x_shape, stride=1, pad=0, dil=1, groups=1, out=None, **kw)
     else:
         if dil != 1:
             raise RuntimeError("conv_dgrad: stride > 1 needs dilation 1")
-        a.s, a.dj, a.off, a.os, a.oo, a.phases = 1, -1, 0, stride, -pad, stride
-        a.Q = (Tin - 1 + pad) // stride + 1
+        _phased(a, stride, pad, Tin)
     _common(a, **kw)
     _launch_conv(a, wt=w)
     return out
@@ -295,9 +261,8 @@ def conv_wgrad(dy, x, w_shape, stride=1, pad=0, dil=1, groups=1, out=None, a_tf=
     if dbias is not None and (_DETERMINISTIC[0] or a_tf != TF_NONE or groups != 1 or min(M, C) == 1):
         bias_grad(dy, aux=aaux, tf=a_tf, slope=slope, out=dbias)
         dbias = None
-    if (groups > 1 and Cg == 4 and K == 41 and stride == 4 and pad == 20 and dil == 1 and P == 1
-            and M // groups in (4, 16) and b_tf == TF_NONE and a_tf in (TF_NONE, TF_DLEAKY) and alpha == 1.0):
-        fn = "vcv_grouped41_wgrad_bf16" if (_COMPUTE[0] == "bf16" and M // groups == 16 and _GROUPED_BF16[0]) else "vcv_grouped41_wgrad"
+    fn = _grouped41("wgrad", groups, M, Cg, K, stride, pad, dil, P)
+    if fn and b_tf == TF_NONE and a_tf in (TF_NONE, TF_DLEAKY) and alpha == 1.0:
         check(getattr(lib(), fn)(ptr(dy), ptr(aaux), ptr(x), ptr(out), B, groups, M // groups, Tin, Tout, a_tf,
                                  slope, stream()), fn)
         return out
@@ -337,8 +302,7 @@ def convT_forward(x, w, bias=None, stride=1, pad=0, out=None, **kw):
     if stride == 1:
         a.s, a.dj, a.off, a.os, a.oo, a.phases, a.Q = 1, -1, pad, 1, 0, 1, Tout
     else:
-        a.s, a.dj, a.off, a.os, a.oo, a.phases = 1, -1, 0, stride, -pad, stride
-        a.Q = (Tout - 1 + pad) // stride + 1
+        _phased(a, stride, pad, Tout)
     _common(a, bias=bias, **kw)
     _launch_conv(a, wt=w)
     return out
@@ -619,15 +583,13 @@ class _ConvFn(torch.autograd.Function):
                 dw = convT_wgrad(dy, x, w3.shape, stride=stride, pad=pad, a_tf=b_tf, b_tf=dtf,
                                  baux=y, slope=slope, out=wout, arena=ctx.w_tmp)
             else:
-                if ctx.has_bias and ctx.needs_input_grad[2] and db_done is None:
-                    # the weight-gradient launch collects sum(dy) while it stages dy
+                # the weight-gradient launch collects sum(dy) while it stages dy
+                with_db = ctx.has_bias and ctx.needs_input_grad[2] and db_done is None
+                if with_db:
                     db_done = ctx.b_sink[0] if ctx.b_sink is not None else torch.zeros((dy.shape[1],), device=dy.device,
                                                                                         dtype=torch.float32)
-                    dw = conv_wgrad(dy, x, w3.shape, stride=stride, pad=pad, dil=dil, groups=groups, a_tf=dtf, aaux=y,
-                                    b_tf=b_tf, slope=slope, out=wout, arena=ctx.w_tmp, dbias=db_done)
-                else:
-                    dw = conv_wgrad(dy, x, w3.shape, stride=stride, pad=pad, dil=dil, groups=groups,
-                                    a_tf=dtf, aaux=y, b_tf=b_tf, slope=slope, out=wout, arena=ctx.w_tmp)
+                dw = conv_wgrad(dy, x, w3.shape, stride=stride, pad=pad, dil=dil, groups=groups, a_tf=dtf, aaux=y,
+                                b_tf=b_tf, slope=slope, out=wout, arena=ctx.w_tmp, dbias=db_done if with_db else None)
             dw = _sunk(ctx.w_sink, dw.view(w.shape))
         if ctx.has_bias and ctx.needs_input_grad[2]:
             if db_done is not None:

@@ -3,6 +3,7 @@ the capture hook and table uploads, layout helpers and the gradient sinks the op
 
 Part of `vcvits_amd.ops` (the package re-exports every name: `from vcvits_amd import ops; ops.conv1d(...)`).  Everything here
 runs on the GPU through libvcvits_hip.so; there is no CPU fallback."""
+import collections
 import ctypes
 
 import torch
@@ -138,10 +139,31 @@ def compute_dtype():
     return _COMPUTE[0]
 
 
+# The packed-weight conv kernel families (csrc/conv_pk*.hip, conv_x3.hip, conv_dma.hip).  A family's name is its
+# LAUNCH_COUNTS key and names its C entry points: vcv_conv_<name>_plan / _run and, where the family's packs can be re-made in
+# one batched launch (vcv_pack_many), vcv_conv_<name>_pack_job.
+ConvFamily = collections.namedtuple("ConvFamily", "name plan run run_name pack_job")
+_BATCHED_PACKS = ("bf16", "x3", "pk")
 _FAMILIES = {}
 
 
-_FAMILY_KEY = {"vcv_conv_bf16_run": "bf16", "vcv_conv_x3_run": "x3", "vcv_conv_pk_run": "pk", "vcv_conv_bf16io_run": "bf16io"}
+def live_families(io=0):
+    """The families a launch with storage combination `io` (VcvConvArgs.io) asks, in order, under the current switches: the
+    16-bit activations have one family; fp32 activations go to the bf16-operand kernel under set_compute_dtype("bf16") or the
+    split-operand kernel (set_f32_split) first, then the packed fp32 kernel, then the LDS-DMA kernel.  Built once per switch
+    setting with the entry points bound (_launch_conv runs ~450 times per step); _FAMILIES.clear() rebinds them."""
+    key = (_COMPUTE[0], _USE_X3[0], _USE_PK[0], io)
+    fams = _FAMILIES.get(key)
+    if fams is None:
+        if io != 0:
+            names = ("bf16io",)
+        else:
+            names = (("bf16",) if _COMPUTE[0] == "bf16" else ("x3",) if _USE_X3[0] else ()) + (("pk",) if _USE_PK[0] else ()) + ("dma",)
+        L = lib()
+        fams = _FAMILIES[key] = tuple(
+            ConvFamily(n, getattr(L, "vcv_conv_%s_plan" % n), getattr(L, "vcv_conv_%s_run" % n), "vcv_conv_%s_run" % n,
+                       getattr(L, "vcv_conv_%s_pack_job" % n) if n in _BATCHED_PACKS else None) for n in names)
+    return fams
 
 
 _DEVS = {}

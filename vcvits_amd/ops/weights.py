@@ -9,8 +9,7 @@ import torch
 
 from .. import tuning
 from .._lib import (VcvConvArgs, check, lib, ptr, stream)
-from .core import (CAPTURING, LAUNCH_COUNTS, _COMPUTE, _USE_PK, _USE_X3, _f32c,
-                   _sink, _upload_table)
+from .core import (CAPTURING, LAUNCH_COUNTS, _f32c, _sink, _upload_table, live_families)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -189,8 +188,43 @@ _PACK_JOBS = {}
 _PACK_BATCH = [tuning.flag("VCVITS_PACK_BATCH", True, "all packs of a module tree re-made in one launch after its weights changed")]
 
 
-_PACK_FILL = {"vcv_conv_x3_run": "vcv_conv_x3_pack_job", "vcv_conv_pk_run": "vcv_conv_pk_pack_job",
-              "vcv_conv_bf16_run": "vcv_conv_bf16_pack_job"}
+def _pack_key(w_ptr, words, sig, wver):
+    """Key of a pack in an entry's cache: the weights' address, the pack's size and layout signature (what the family's
+    _plan returned) and, in a parameter region, the weight tensor's version the pack was made from (0 elsewhere)."""
+    return (w_ptr, words, sig) if wver == 0 else (w_ptr, words, sig, wver)
+
+
+def _packed_weights(a, flip, plan, fam, wt, dev):
+    """(buffer, valid) for the packed weights of launch `a`, which family `fam` planned as `plan`: the cached pack of the
+    weight-norm buffer / parameter region that holds a.w (valid: the launch skips its pack pass), else a new buffer, which is
+    cached where there is such an entry.  wt: the weight tensor, for its version."""
+    ent = _stable_entry(a.w)
+    wver = 0
+    if ent is not None and "dirty" in ent:
+        # a parameter region: the pack is valid for the weight tensor's version it was made from (an in-place write
+        # that did not go through the optimizer bumps it); callers that do not hand the tensor over pack per use
+        if wt is None:
+            ent = None
+        else:
+            wver = wt._version
+    if ent is None:
+        return torch.empty((plan[0],), device=dev, dtype=torch.float32), 0
+    key = _pack_key(a.w, plan[0], plan[2], wver)
+    pack = ent["packs"].get(key)
+    if pack is not None:
+        return pack, 1
+    pack = ent["packs"][key] = torch.empty((plan[0],), device=dev, dtype=torch.float32)
+    # remember the job: the next time this tree's weights are re-normalised all of its packs are made in one launch
+    # (_replay_packs)
+    if len(_PACK_JOBS) > 64:
+        _PACK_JOBS.clear()
+    jobs = _PACK_JOBS.get(ent["key"])
+    if jobs is None or jobs["shapes"] != ent["shapes"]:  # (a recycled address set is another module's)
+        jobs = _PACK_JOBS[ent["key"]] = {"shapes": ent["shapes"], "jobs": {}}
+    # (a region's job remembers the tensor version it was recorded at: the optimizer's raw update leaves versions alone, so
+    # the replay registers the pack under the version the next use will ask for)
+    jobs["jobs"][(a.w - ent["lo"], int(plan[0]), int(plan[2]), fam.name)] = (bytes(a), flip, wver)
+    return pack, 0
 
 
 def _replay_packs(key, ent):
@@ -205,13 +239,9 @@ def _replay_packs(key, ent):
     from .._lib import VcvPackJob
     L = lib()
     # only the families the current switches can launch (a job of another arithmetic would be packed for nothing)
-    live = {"vcv_conv_pk_run"} if _USE_PK[0] else set()
-    if _COMPUTE[0] == "bf16":
-        live.add("vcv_conv_bf16_run")
-    elif _USE_X3[0]:
-        live.add("vcv_conv_x3_run")
+    fill = {f.name: f.pack_job for f in live_families() if f.pack_job is not None}
     span = ent["hi"] - ent["lo"]
-    todo = [(k, v) for k, v in rec["jobs"].items() if k[3] in _PACK_FILL and k[3] in live]
+    todo = [(k, v) for k, v in rec["jobs"].items() if k[3] in fill]
     if not todo:
         return
     arr = (VcvPackJob * len(todo))()
@@ -227,11 +257,11 @@ def _replay_packs(key, ent):
         if woff < 0 or woff + 4 * a.Mg * a.Cg * a.K > span:
             continue
         a.w = ent["lo"] + woff
-        if getattr(L, _PACK_FILL[fam])(ctypes.byref(a), flip, ctypes.byref(arr[n])) != 0:
+        if fill[fam](ctypes.byref(a), flip, ctypes.byref(arr[n])) != 0:
             continue  # (the plan no longer takes this launch, e.g. a mode switch: it will pack lazily)
         view = arena[off:off + words]
         arr[n].w, arr[n].wp = a.w, view.data_ptr()
-        reg.append(((a.w, words, sig) if wver == 0 else (a.w, words, sig, wver), view))
+        reg.append((_pack_key(a.w, words, sig, wver), view))
         off += (words + 31) & ~31  # 128-byte aligned slices
         n += 1
     if n == 0:

@@ -10,7 +10,7 @@ import torch
 from .. import tuning
 from .._lib import (ACT_NONE, TF_LEAKY, TF_NONE, VcvConvArgs, check, lib, ptr, stream)
 from .core import (LAUNCH_COUNTS, _f32c, _rows, conv_out_len)
-from .conv import (_common, _launch_conv, convT_out_len)
+from .conv import (_common, _launch_conv, _phased, convT_out_len)
 from .weights import (_stable_entry)
 
 
@@ -98,11 +98,9 @@ def convT_forward_x16(x, w, bias=None, stride=1, pad=0, in_leaky=False, slope=0.
         # all `stride` output phases as rows (cout, phase) of ONE launch: one staged input span feeds every phase and the
         # epilogue writes runs of consecutive samples (VcvConvArgs.ms)
         a.Mg, a.K, a.ms = M * stride, K // stride, stride
-        a.s, a.dj, a.off, a.os, a.oo, a.phases = 1, -1, 0, stride, -pad, 1
-        a.Q = (Tout - 1 + pad) // stride + 1
+        _phased(a, stride, pad, Tout, phases=1)
     else:
-        a.s, a.dj, a.off, a.os, a.oo, a.phases = 1, -1, 0, stride, -pad, stride
-        a.Q = (Tout - 1 + pad) // stride + 1
+        _phased(a, stride, pad, Tout)
     _common(a, bias=_f32c(bias), in_tf=TF_LEAKY if in_leaky else TF_NONE, slope=slope)
     a.io = _io_bits(x, out)
     _launch_conv(a)
