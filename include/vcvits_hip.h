@@ -648,6 +648,14 @@ int vcv_hubert_bias_gelu(const float* x, const float* bias, const float* res, fl
 /* gelu(GroupNorm(C, C)(x)): statistics per (b, c) over T, summed in float64; y may be x */
 int vcv_hubert_groupnorm_gelu(const float* x, const float* gamma, const float* beta, float* y, int B, int C, int T,
                               float eps, void* stream);
+/* The same with one sample count per batch row: counts is a device array of B ints in [1, T] (values outside are clamped).
+ * The float64 sums run over t < counts[b] and samples behind the count are never read; y[b, c, t] is the normalised GELU
+ * for t < counts[b] and exact 0 behind it.  A count of 1 has variance 0 and gives gelu(beta).  y may be x. */
+int vcv_hubert_groupnorm_gelu_len(const float* x, const float* gamma, const float* beta, float* y, int B, int C, int T,
+                                  const int* counts, float eps, void* stream);
+/* y[b, c, t] = t < frames[b] ? x[b, c, t] : 0 with frames a device array of B ints: a select (NaN behind a row's end becomes
+ * 0), one streaming pass; y may be x */
+int vcv_hubert_mask_frames(const float* x, float* y, int B, int C, int T, const int* frames, void* stream);
 /* gelu(LayerNorm over C of x[b, :, t]), statistics in float64; y may be x */
 int vcv_hubert_layernorm_c_gelu(const float* x, const float* gamma, const float* beta, float* y, int B, int C, int T,
                                 float eps, void* stream);
@@ -658,6 +666,12 @@ int vcv_hubert_layernorm_c_gelu(const float* x, const float* gamma, const float*
 int vcv_hubert_attn_supported(int B, int H, int dk, int T);
 int vcv_hubert_attn_fwd(const float* q, const float* k, const float* v, float* out, int B, int H, int dk, int T, int64_t ldb,
                         float scale, void* stream);
+/* The same with a key bound per batch row: frames is a device array of B ints, and a head of row b attends to the keys
+ * s < frames[b] only.  PRECONDITION: 1 <= frames[b] <= T (the running max needs key 0 to exist; the caller checks its host
+ * copy, and the kernel clamps into the range so that a bad value cannot read out of bounds).  Keys, values and queries at
+ * t >= frames[b] are never used, whatever they hold; out[b, :, t] is exact 0 for t >= frames[b]. */
+int vcv_hubert_attn_fwd_len(const float* q, const float* k, const float* v, float* out, int B, int H, int dk, int T,
+                            int64_t ldb, float scale, const int* frames, void* stream);
 
 /* returns a static string describing the build (arch, kernel variants) */
 const char* vcv_version(void);

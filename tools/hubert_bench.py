@@ -13,6 +13,14 @@ One JSON line per (architecture, mode):
 
     python tools/hubert_bench.py [--arch base,xtralarge] [--batch 16] [--seconds 10] [--modes f32,bf16] [--out FILE]
 
+--ragged replaces those lines by one line per mode for rows of unequal length (base widths, 12 layers, 16 rows whose padded
+lengths are spread evenly over 3 to 10 s), extract_features(lengths=) and preprocess.hubert_features_batch:
+  files      audio-s/s of hubert_features_batch over the 16 files against hubert_features file by file (wall time, host
+             copies included: what filling the feature cache costs)
+  padded     ms per batch of the padded [16, 10 s] batch with lengths= and without (without, the rows are not the rows alone)
+  equal      ms per batch of 16 equal rows of 10 s with lengths= (all rows full) and without
+Every pair is measured as alternating runs in one process, three each; the median and the range (min, max) are reported.
+
 There is no CPU path: without a GPU this fails."""
 import argparse
 import json
@@ -140,6 +148,81 @@ def bench(arch, mode, batch, seconds, steps, warmup):
     return line
 
 
+def _stats(v):
+    v = sorted(v)
+    return {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3), "max": round(v[-1], 3)}
+
+
+def _alternate(fa, fb, runs=3):
+    """fa and fb (each returns one figure) as alternating runs; (stats of fa, stats of fb)"""
+    a, b = [], []
+    for _ in range(runs):
+        a.append(fa())
+        b.append(fb())
+    return _stats(a), _stats(b)
+
+
+def ragged(mode, steps, warmup, rows=16, shortest=3.0, longest=10.0):
+    import time
+
+    from vcvits_amd.preprocess import hubert_features, hubert_features_batch
+    torch.manual_seed(0)
+    model = HubertFeatureExtractor(**ARCHS["base"]).to("cuda")
+    g = torch.Generator().manual_seed(1)
+    # padded rows (40 + 40 samples around a file) of 3 .. 10 s: the longest batch is the default budget of 16 x 10 s
+    lengths = [int(round((shortest + (longest - shortest) * i / (rows - 1)) * 16000)) for i in range(rows)]
+    audios = [0.1 * torch.randn(1, n - 80, generator=g) for n in lengths]
+    T = lengths[-1]
+    padded = torch.zeros(rows, T)
+    for b, a in enumerate(audios):
+        padded[b, 40:40 + a.shape[1]] = a[0]
+    padded = padded.to("cuda")
+    equal = (0.1 * torch.randn(rows, T, generator=g)).to("cuda")
+    audio_s = sum(lengths) / 16000.0
+
+    def wall(fn):
+        def run():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            return audio_s / (time.perf_counter() - t0)
+        return run
+
+    def per_batch(src, lens):
+        def run():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(steps):
+                model.extract_features(src, lengths=lens)
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / steps
+        return run
+
+    ops.set_compute_dtype("bf16" if mode == "bf16" else "f32")
+    try:
+        legs = {"files": (wall(lambda: hubert_features_batch(model, audios)), wall(lambda: [hubert_features(model, a) for a in audios])),
+                "padded": (per_batch(padded, lengths), per_batch(padded, None)),
+                "equal": (per_batch(equal, [T] * rows), per_batch(equal, None))}
+        out = {}
+        for name, (fa, fb) in legs.items():
+            for _ in range(warmup):
+                fa()
+                fb()
+            out[name] = _alternate(fa, fb)
+        feats, pm = model.extract_features(padded, lengths=lengths)
+        finite = bool(torch.isfinite(feats).all())
+    finally:
+        ops.set_compute_dtype("f32")
+    return {"tool": "hubert_bench", "leg": "ragged", "arch": "base", "mode": mode, "layers": ARCHS["base"]["layers"], "rows": rows,
+            "row_seconds": [shortest, longest], "audio_s": round(audio_s, 2), "valid_fraction": round(sum(lengths) / (rows * T), 3),
+            "files_audio_s_per_s": {"hubert_features_batch": out["files"][0], "hubert_features_one_at_a_time": out["files"][1]},
+            "padded_ms_per_batch": {"lengths": out["padded"][0], "no_lengths": out["padded"][1]},
+            "equal_ms_per_batch": {"lengths_all_full": out["equal"][0], "no_lengths": out["equal"][1]},
+            "finite": finite, "device": torch.cuda.get_device_name(0)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--arch", default="base,xtralarge")
@@ -149,9 +232,19 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None, help="append the JSON lines to this file as well")
+    ap.add_argument("--ragged", action="store_true", help="the rows-of-unequal-length leg (base x 12 layers) instead")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("hubert_bench: no GPU (there is no CPU path to time)")
+    if args.ragged:
+        for mode in args.modes.split(","):
+            line = json.dumps(ragged(mode, args.steps, args.warmup))
+            print(line, flush=True)
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(line + "\n")
+            torch.cuda.empty_cache()
+        return 0
     for arch in args.arch.split(","):
         for mode in args.modes.split(","):
             line = json.dumps(bench(arch, mode, args.batch, args.seconds, args.steps, args.warmup))

@@ -4,6 +4,16 @@
 //   * LayerNorm over channels fused with GELU (every layer of the large models' front end);
 //   * bias + exact GELU (+ residual) as one streaming pass.
 // Everything is [B, C, T] float32 with T contiguous, as in the rest of the library.
+//
+// Rows of unequal length in one padded batch (extract_features(lengths=)): the features of a row are those of the row
+// computed alone.  Three entry points carry a device array of one int per batch row for that, and everything else of the
+// model is per frame already (frames past a row's end may hold anything there: nothing valid reads them):
+//   * vcv_hubert_groupnorm_gelu_len  statistics over the first counts[b] samples of a row, exact 0 written behind them;
+//   * vcv_hubert_mask_frames         y = t < frames[b] ? x : 0, on the input of the position conv (a row alone sees zero
+//                                    padding there) and on the final features;
+//   * vcv_hubert_attn_fwd_len        keys s < frames[b] only, exact 0 for the queries behind them.
+// All three select, never multiply: NaN or Inf behind a row's end does not reach a valid frame.  The entry points without
+// lengths are the same kernels instantiated without the array, with the instructions they had before it existed.
 #include "common.h"
 #include <math.h>
 
@@ -33,18 +43,36 @@ hubert_bias_gelu_kernel(const float* x, const float* __restrict__ bias, const fl
   y[i] = v;
 }
 
+// ---- y[b, c, t] = t < frames[b] ? x[b, c, t] : 0 (a select: whatever lies behind a row's end becomes exact 0, NaN
+// included); one streaming pass, y may be x ---------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+hubert_mask_frames_kernel(const float* x, float* y, int C, int T, const int* __restrict__ frames, size_t n) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const size_t r = i / (size_t)T;
+  const int t = (int)(i - r * (size_t)T);
+  float v = 0.f;
+  if (t < frames[r / (size_t)C]) v = x[i];
+  y[i] = v;
+}
+
 // ---- GroupNorm(C, C) + GELU: one block per (b, c) row of T samples.  Pass 1 sums x and x^2 in float64 (a row of the base
 // model's first layer has 1e5 - 1e6 samples, and a float32 sum of squares loses the variance as soon as the row has an
 // offset); pass 2 re-reads the row (from L2 while it fits), subtracts the mean as a two-float value, and writes once.
-// y may be x. -----------------------------------------------------------------------------------------------------------
+// y may be x.  LEN: the statistics and the normalised output cover the first n = counts[b] samples of the row (clamped to
+// [1, T]; samples behind them are never read), and y[n .. T) is written as exact 0.  n = 1 has variance 0 and yields
+// gelu(beta).  Without LEN n is T and the code is what it was. -----------------------------------------------------------
+template <bool LEN>
 __global__ void __launch_bounds__(256)
 hubert_groupnorm_gelu_kernel(const float* x, const float* __restrict__ gamma, const float* __restrict__ beta, float* y,
-                             int C, int T, float eps) {
+                             int C, int Trow, float eps, const int* __restrict__ counts) {
   __shared__ double red[2][4];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const size_t row = blockIdx.x;
-  const float* xr = x + row * (size_t)T;
-  float* yr = y + row * (size_t)T;
+  const float* xr = x + row * (size_t)Trow;
+  float* yr = y + row * (size_t)Trow;
+  int T = Trow;  // the samples that count
+  if (LEN) T = min(max(counts[row / (size_t)C], 1), Trow);
   // 16-byte loads over the aligned middle of the row when x and y rows are misaligned alike, scalars around it
   int head = (int)((4 - (((uintptr_t)xr >> 2) & 3)) & 3);
   if ((((uintptr_t)xr ^ (uintptr_t)yr) & 15) != 0 || head > T) head = T;
@@ -82,6 +110,8 @@ hubert_groupnorm_gelu_kernel(const float* x, const float* __restrict__ gamma, co
     y4[i] = v;
   }
   for (int i = tail0 + tid; i < T; i += 256) yr[i] = hubert_gelu(((xr[i] - mhi) - mlo) * g + bt);
+  if (LEN)
+    for (int i = T + tid; i < Trow; i += 256) yr[i] = 0.f;
 }
 
 // ---- LayerNorm over C + GELU for [B, C, T]: a block is 64 consecutive t (lanes) x 4 channel groups (waves); one pass
@@ -128,11 +158,16 @@ hubert_layernorm_c_gelu_kernel(const float* x, const float* __restrict__ gamma, 
 // S^T leaves the matrix pipe with the query on the lane and 16 of the tile's 32 keys in the lane's registers (the other 16
 // in lane ^ 32), so the running max / sum of a query is a loop over registers plus one cross-lane exchange, and register r
 // is already the B operand of the k-pair {row(r, half 0), row(r, half 1)} of the second product: no LDS round trip for P,
-// nothing of size T x T anywhere.  D = 80 pads the value tile to 96 rows of zeros (3 output tiles of 32 channels). -------
-template <int D>
+// nothing of size T x T anywhere.  D = 80 pads the value tile to 96 rows of zeros (3 output tiles of 32 channels).
+// LEN: a head of batch row b sees the keys s < n = frames[b] only (precondition 1 <= frames[b] <= T, so key 0 exists; the
+// value is clamped into that range, so a bad one cannot read out of bounds).  The key loop ends at n, keys / values and
+// queries at or behind n are staged as 0 by a select (whatever is stored there, NaN included, is never used), their scores
+// are -inf, and the output of the queries t >= n is exact 0.  A block whose 128 queries all lie behind n writes its zeros
+// and leaves before the first barrier (n is uniform over the block).  Without LEN n is T and the code is what it was. ------
+template <int D, bool LEN>
 __global__ void __launch_bounds__(256)
 hubert_attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-                       float* __restrict__ out, int H, int T, size_t ldb, float scale) {
+                       float* __restrict__ out, int H, int T, size_t ldb, float scale, const int* __restrict__ frames) {
   constexpr int DT = (D + 31) / 32;  // output tiles of 32 channels
   constexpr int VS = 33;             // row stride of the value tile: its A fragments walk d across lanes
   __shared__ float Ks[D * 32];
@@ -143,10 +178,21 @@ hubert_attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
   const size_t obase = (size_t)blockIdx.y * D * T;
   const int t = blockIdx.x * 128 + wv * 32 + col;
   const bool tok = t < T;
+  int n = T;  // keys (and queries) that exist
+  if (LEN) {
+    n = min(max(frames[blockIdx.y / H], 1), T);
+    if ((int)blockIdx.x * 128 >= n) {
+      if (tok)
+#pragma unroll
+        for (int i = 0; i < D / 2; ++i) out[obase + (size_t)(2 * i + hf) * T + t] = 0.f;
+      return;
+    }
+  }
+  const bool qok = t < n;
 
   float qr[D / 2];
 #pragma unroll
-  for (int i = 0; i < D / 2; ++i) qr[i] = tok ? q[base + (size_t)(2 * i + hf) * T + t] * scale : 0.f;
+  for (int i = 0; i < D / 2; ++i) qr[i] = qok ? q[base + (size_t)(2 * i + hf) * T + t] * scale : 0.f;
   for (int i = D * VS + tid; i < DT * 32 * VS; i += 256) Vs[i] = 0.f;
 
   f32x16 o[DT];
@@ -157,11 +203,11 @@ hubert_attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
   float m = -INFINITY, l = 0.f;
 
   const int sd = tid >> 5, sc = tid & 31;
-  for (int s0 = 0; s0 < T; s0 += 32) {
+  for (int s0 = 0; s0 < n; s0 += 32) {
     __syncthreads();  // the previous tile has been read
     {
       const int s = s0 + sc;
-      const bool sok = s < T;
+      const bool sok = s < n;
 #pragma unroll
       for (int i = 0; i < D / 8; ++i) {
         const int d = sd + 8 * i;
@@ -182,7 +228,7 @@ hubert_attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int s = s0 + (r & 3) + 8 * (r >> 2) + 4 * hf;
-      if (s >= T) S[r] = -INFINITY;
+      if (s >= n) S[r] = -INFINITY;
       mx = fmaxf(mx, S[r]);
     }
     mx = fmaxf(mx, __shfl_xor(mx, 32));
@@ -215,7 +261,7 @@ hubert_attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int d = j * 32 + (r & 3) + 8 * (r >> 2) + 4 * hf;
-      if (d < D) out[obase + (size_t)d * T + t] = o[j][r] * inv;
+      if (d < D) out[obase + (size_t)d * T + t] = (!LEN || qok) ? o[j][r] * inv : 0.f;
     }
 }
 
@@ -236,7 +282,25 @@ extern "C" int vcv_hubert_groupnorm_gelu(const float* x, const float* gamma, con
   if (!x || !gamma || !beta || !y || B <= 0 || C <= 0 || T <= 0) return VCV_EINVAL;
   const long long rows = (long long)B * C;
   if (rows > 0x7fffffffLL) return VCV_EINVAL;
-  hubert_groupnorm_gelu_kernel<<<(unsigned)rows, 256, 0, (hipStream_t)stream>>>(x, gamma, beta, y, C, T, eps);
+  hubert_groupnorm_gelu_kernel<false><<<(unsigned)rows, 256, 0, (hipStream_t)stream>>>(x, gamma, beta, y, C, T, eps, nullptr);
+  return vcv_check_launch();
+}
+
+extern "C" int vcv_hubert_groupnorm_gelu_len(const float* x, const float* gamma, const float* beta, float* y, int B, int C,
+                                             int T, const int* counts, float eps, void* stream) {
+  if (!x || !gamma || !beta || !y || !counts || B <= 0 || C <= 0 || T <= 0) return VCV_EINVAL;
+  const long long rows = (long long)B * C;
+  if (rows > 0x7fffffffLL) return VCV_EINVAL;
+  hubert_groupnorm_gelu_kernel<true><<<(unsigned)rows, 256, 0, (hipStream_t)stream>>>(x, gamma, beta, y, C, T, eps, counts);
+  return vcv_check_launch();
+}
+
+extern "C" int vcv_hubert_mask_frames(const float* x, float* y, int B, int C, int T, const int* frames, void* stream) {
+  if (!x || !y || !frames || B <= 0 || C <= 0 || T <= 0) return VCV_EINVAL;
+  const size_t n = (size_t)B * C * T;
+  const size_t blocks = (n + 255) / 256;
+  if (blocks > 0x7fffffffULL) return VCV_EINVAL;
+  hubert_mask_frames_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, y, C, T, frames, n);
   return vcv_check_launch();
 }
 
@@ -257,8 +321,20 @@ extern "C" int vcv_hubert_attn_fwd(const float* q, const float* k, const float* 
   if (!q || !k || !v || !out || vcv_hubert_attn_supported(B, H, dk, T) != 0 || ldb < (int64_t)H * dk * T) return VCV_EINVAL;
   const dim3 grid(vcv_cdiv(T, 128), B * H);
   if (dk == 64)
-    hubert_attn_fwd_kernel<64><<<grid, 256, 0, (hipStream_t)stream>>>(q, k, v, out, H, T, (size_t)ldb, scale);
+    hubert_attn_fwd_kernel<64, false><<<grid, 256, 0, (hipStream_t)stream>>>(q, k, v, out, H, T, (size_t)ldb, scale, nullptr);
   else
-    hubert_attn_fwd_kernel<80><<<grid, 256, 0, (hipStream_t)stream>>>(q, k, v, out, H, T, (size_t)ldb, scale);
+    hubert_attn_fwd_kernel<80, false><<<grid, 256, 0, (hipStream_t)stream>>>(q, k, v, out, H, T, (size_t)ldb, scale, nullptr);
+  return vcv_check_launch();
+}
+
+extern "C" int vcv_hubert_attn_fwd_len(const float* q, const float* k, const float* v, float* out, int B, int H, int dk, int T,
+                                       int64_t ldb, float scale, const int* frames, void* stream) {
+  if (!q || !k || !v || !out || !frames || vcv_hubert_attn_supported(B, H, dk, T) != 0 || ldb < (int64_t)H * dk * T)
+    return VCV_EINVAL;
+  const dim3 grid(vcv_cdiv(T, 128), B * H);
+  if (dk == 64)
+    hubert_attn_fwd_kernel<64, true><<<grid, 256, 0, (hipStream_t)stream>>>(q, k, v, out, H, T, (size_t)ldb, scale, frames);
+  else
+    hubert_attn_fwd_kernel<80, true><<<grid, 256, 0, (hipStream_t)stream>>>(q, k, v, out, H, T, (size_t)ldb, scale, frames);
   return vcv_check_launch();
 }

@@ -8,9 +8,16 @@ feature cache (preprocess.py:18-22, 60-74).  This module is that model for the t
                                         16 x 64 / 16 x 80
 
 Parameters carry fairseq's state_dict names, so `ckpt["model"]` loads as it is; the pre-training heads (mask_emb,
-label_embs_concat, final_proj) are not part of the model.  Inference only: no masking, no padding mask, no dropout, no
-gradients.  Rows of a batch are computed as fairseq computes them without a padding mask (the zeros behind a shorter row
-take part in the norms and in the attention).
+label_embs_concat, final_proj) are not part of the model.  Inference only: no masking, no dropout, no gradients.
+
+Rows of unequal length.  Without `lengths=` the rows of a batch are computed as fairseq computes them without a padding
+mask: the zeros behind a shorter row take part in the layer-0 GroupNorm, the position conv and every attention softmax.
+With `extract_features(source, lengths=)` the features of a row in a padded batch are the features of that row computed
+alone: the GroupNorm statistics are counted per row, the frames behind a row's end are zeroed before the position conv
+(the padding a row alone sees there), the attention keys are bounded per row, and the features behind a row's end come
+back as exact zeros with a frame padding mask.  Everything between those steps is per frame, and nothing valid reads a
+frame behind a row's end.  This is NOT fairseq's `padding_mask`: fairseq keeps the padded zeros in the GroupNorm and
+derives the frame mask by a chunking rule, so `padding_mask=` stays unbuilt and raises.
 
 The tensor layout is [B, C, T] throughout.  Every linear layer and convolution is ops.conv_forward (so they follow
 set_compute_dtype: split-operand fp32 or bf16 operands), residual + LayerNorm is ops.layernorm_c, and attention, GroupNorm +
@@ -124,7 +131,8 @@ class _Bag(nn.Module):
 
 class HubertFeatureExtractor(nn.Module):
     """extract_features(source [B, T]) -> (features [B, T', embed_dim], None), T' = the conv stack's output length
-    ((T - 400) // 320 + 1 with the published kernels and strides)."""
+    ((T - 400) // 320 + 1 with the published kernels and strides); with lengths= (valid samples per row) the second element
+    is the frame padding mask [B, T'] and every row equals that row computed alone."""
 
     def __init__(self, conv_dim=512, embed_dim=768, ffn_dim=3072, layers=12, heads=12, extractor_mode="default",
                  layer_norm_first=False, conv_bias=False, conv_kernels=CONV_KERNELS, conv_strides=CONV_STRIDES,
@@ -253,6 +261,39 @@ class HubertFeatureExtractor(nn.Module):
             t = (t - k) // s + 1 if t >= k else 0
         return t
 
+    def receptive_field(self):
+        """Samples that give one output frame (400 with the published kernels and strides)."""
+        need = 1
+        for k, s in zip(reversed(self.conv_kernels), reversed(self.conv_strides)):
+            need = (need - 1) * s + k
+        return need
+
+    def frame_lengths(self, lengths):
+        """Output frames of rows with `lengths` valid samples (a list or an integer tensor): out_frames per entry, as an
+        int64 CPU tensor of the same shape."""
+        t = torch.as_tensor(lengths).detach().to("cpu")
+        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise ValueError("lengths must be integers, got %s" % t.dtype)
+        return torch.tensor([self.out_frames(v) for v in t.reshape(-1).tolist()], dtype=torch.int64).reshape(t.shape)
+
+    def _check_lengths(self, lengths, B, T):
+        """The host copy (int64 CPU [B]) of `lengths`, checked; every failure is a ValueError that names the row."""
+        t = torch.as_tensor(lengths).detach()
+        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise ValueError("lengths must hold one integer sample count per row of source, got dtype %s" % t.dtype)
+        if tuple(t.shape) != (B,):
+            raise ValueError("lengths must hold one sample count per row of source: shape [%d] expected, got %s"
+                             % (B, list(t.shape)))
+        host = t.to("cpu", torch.int64)  # the one copy to the host when lengths lives on the GPU
+        need = self.receptive_field()
+        for b, v in enumerate(host.tolist()):
+            if v > T:
+                raise ValueError("lengths[%d] = %d: row %d cannot be longer than source (%d samples)" % (b, v, b, T))
+            if v < need:
+                raise ValueError("lengths[%d] = %d: row %d is shorter than the conv stack's receptive field (%d)"
+                                 % (b, v, b, need))
+        return host
+
     def _weights(self, device):
         """{name: float32 view} of the conv-ready weights on `device`, all inside one flat buffer that is registered as a
         parameter region (ops.register_param_region: the conv kernels' packed copies are cached per region).  Rebuilt when a
@@ -304,15 +345,23 @@ class HubertFeatureExtractor(nn.Module):
                 pass
 
     # ------------------------------------------------------------------------------------------------------ forward
-    def _attn_block(self, w, p, x):
-        return ops.hubert_attention_qkv(ops.conv_forward(x, w[p + ".qkv.weight"], w[p + ".qkv.bias"]), self.heads)
+    def _attn_block(self, w, p, x, fr=None):
+        return ops.hubert_attention_qkv(ops.conv_forward(x, w[p + ".qkv.weight"], w[p + ".qkv.bias"]), self.heads, lengths=fr)
 
-    def extract_features(self, source, padding_mask=None, mask=False, output_layer=None):
+    def extract_features(self, source, padding_mask=None, mask=False, output_layer=None, lengths=None):
         """fairseq's HubertModel.extract_features for inference: source [B, T] float32 on the GPU ->
         (features [B, T', embed_dim], None).  output_layer None: the encoder output; n (1-based): the output of layer n (a
-        pre-LN model then skips the final encoder.layer_norm, as fairseq does)."""
+        pre-LN model then skips the final encoder.layer_norm, as fairseq does).
+
+        lengths (a list, a CPU tensor or a GPU tensor of B integers): the valid samples of each row of a padded batch, each
+        between the receptive field of the conv stack and T.  The result is then (features, frame_padding_mask [B, T'] bool,
+        True where a frame is padding), the valid frames of row b (frame_lengths(lengths)[b] of them) are what
+        extract_features(source[b:b + 1, :lengths[b]]) gives, and the features under the mask are exact zeros, whatever the
+        samples behind a row's end hold.  The per-layer counts are computed on the host, so lengths on the GPU costs one
+        copy to the host (and a wait for the queue); a list or a CPU tensor costs none."""
         if padding_mask is not None:
-            raise NotImplementedError("HubertFeatureExtractor: padding masks are not built (the reference passes none)")
+            raise NotImplementedError("HubertFeatureExtractor: fairseq's padding masks are not built (the reference passes "
+                                      "none); for rows of unequal length pass lengths=")
         if mask:
             raise NotImplementedError("HubertFeatureExtractor: masking is a pre-training feature; inference only")
         if not isinstance(source, torch.Tensor) or source.dim() != 2:
@@ -322,14 +371,23 @@ class HubertFeatureExtractor(nn.Module):
         B, T = source.shape
         frames = self.out_frames(T)
         if frames < 1:
-            need = 1
-            for k, s in zip(reversed(self.conv_kernels), reversed(self.conv_strides)):
-                need = (need - 1) * s + k
-            raise ValueError("source of %d samples is shorter than the conv stack's receptive field (%d)" % (T, need))
+            raise ValueError("source of %d samples is shorter than the conv stack's receptive field (%d)"
+                             % (T, self.receptive_field()))
+        host = None if lengths is None else self._check_lengths(lengths, B, T)
         if not source.is_cuda:
             raise RuntimeError("vcvits_amd: source is not on the GPU; the HIP path has no CPU fallback")
         with torch.no_grad():
             w = self._weights(source.device)
+            n0 = fr = pad_mask = None
+            if host is not None:
+                # what the kernels need of the lengths: layer 0's output samples per row (the GroupNorm counts) and the
+                # output frames per row, both >= 1 after _check_lengths; one upload
+                k0, s0 = self.conv_kernels[0], self.conv_strides[0]
+                fr_host = self.frame_lengths(host)
+                # (from pinned memory and without waiting: a pageable copy would hold the host until the queue has drained)
+                dev = torch.stack([(host - k0) // s0 + 1, fr_host]).to(torch.int32).pin_memory().to(source.device, non_blocking=True)
+                n0, fr = dev[0], dev[1]
+                pad_mask = (torch.arange(frames)[None, :] >= fr_host[:, None]).pin_memory().to(source.device, non_blocking=True)
             x = source.detach().to(torch.float32).contiguous().unsqueeze(1)
             for i, s in enumerate(self.conv_strides):
                 p = "feature_extractor.conv_layers.%d" % i
@@ -337,11 +395,13 @@ class HubertFeatureExtractor(nn.Module):
                 if self.extractor_mode == "layer_norm":
                     x = ops.layernorm_c_gelu(x, w[p + ".2.1.weight"], w[p + ".2.1.bias"], EPS, inplace=True)
                 elif i == 0:
-                    x = ops.groupnorm_gelu(x, w[p + ".2.weight"], w[p + ".2.bias"], EPS, inplace=True)
+                    x = ops.groupnorm_gelu(x, w[p + ".2.weight"], w[p + ".2.bias"], EPS, inplace=True, lengths=n0)
                 else:
                     x = ops.bias_gelu(x, inplace=True)
             x = ops.layernorm_c(x, None, w["layer_norm.weight"], w["layer_norm.bias"], EPS)
             x = ops.conv_forward(x, w["post_extract_proj.weight"], w["post_extract_proj.bias"])
+            if fr is not None:  # the position conv of a row alone sees zeros behind the row's end
+                x = ops.mask_frames(x, fr, inplace=True)
             pos = ops.conv_forward(x, w["encoder.pos_conv.0.weight"], w["encoder.pos_conv.0.bias"], pad=self.conv_pos // 2,
                                    groups=self.conv_pos_groups)  # an even kernel yields one frame too many: dropped below
             if self.layer_norm_first:
@@ -356,19 +416,21 @@ class HubertFeatureExtractor(nn.Module):
                 ln2 = (w[p + ".final_layer_norm.weight"], w[p + ".final_layer_norm.bias"])
                 ow, ob = w[p + ".self_attn.out_proj.weight"], w[p + ".self_attn.out_proj.bias"]
                 if self.layer_norm_first:
-                    a = self._attn_block(w, p + ".self_attn", ops.layernorm_c(x, None, ln1[0], ln1[1], EPS))
+                    a = self._attn_block(w, p + ".self_attn", ops.layernorm_c(x, None, ln1[0], ln1[1], EPS), fr)
                     x = ops.conv_forward(a, ow, ob, res=x)
                     h = ops.conv_forward(ops.layernorm_c(x, None, ln2[0], ln2[1], EPS), w[p + ".fc1.weight"], w[p + ".fc1.bias"])
                     x = ops.conv_forward(ops.bias_gelu(h, inplace=True), w[p + ".fc2.weight"], w[p + ".fc2.bias"], res=x)
                 else:
-                    a = ops.conv_forward(self._attn_block(w, p + ".self_attn", x), ow, ob)
+                    a = ops.conv_forward(self._attn_block(w, p + ".self_attn", x, fr), ow, ob)
                     x = ops.layernorm_c(x, a, ln1[0], ln1[1], EPS)
                     h = ops.conv_forward(x, w[p + ".fc1.weight"], w[p + ".fc1.bias"])
                     h = ops.conv_forward(ops.bias_gelu(h, inplace=True), w[p + ".fc2.weight"], w[p + ".fc2.bias"])
                     x = ops.layernorm_c(x, h, ln2[0], ln2[1], EPS)
             if self.layer_norm_first and output_layer is None:
                 x = ops.layernorm_c(x, None, w["encoder.layer_norm.weight"], w["encoder.layer_norm.bias"], EPS)
-            return x.transpose(1, 2).contiguous(), None
+            if fr is not None:
+                x = ops.mask_frames(x, fr, inplace=True)
+            return x.transpose(1, 2).contiguous(), pad_mask
 
-    def forward(self, source, padding_mask=None, mask=False, output_layer=None):
-        return self.extract_features(source, padding_mask=padding_mask, mask=mask, output_layer=output_layer)
+    def forward(self, source, padding_mask=None, mask=False, output_layer=None, lengths=None):
+        return self.extract_features(source, padding_mask=padding_mask, mask=mask, output_layer=output_layer, lengths=lengths)

@@ -2,6 +2,12 @@
 LayerNorm + GELU, bias + GELU (+ residual).  With conv_forward (every linear layer and convolution) and layernorm_c these
 are all of fairseq's HubertModel.extract_features (vcvits_amd/model/hubert.py).
 
+Rows of unequal length in one padded batch: `hubert_attention(_qkv)` and `groupnorm_gelu` take `lengths=`, an int32 [B] tensor
+on the GPU (keys, or samples, that exist in each row), and `mask_frames` zeroes what lies behind a row's end.  All three
+select and never multiply, so nothing stored behind a row's end reaches a valid frame.  With `lengths=None` every function
+is what it was.  The entries must lie in [1, T]: the wrappers do not read the tensor back (that would stall the queue once
+per layer), the model checks its host copy before it uploads it, and the kernels clamp a value outside the range.
+
 Part of `vcvits_amd.ops` (the package re-exports every name: `from vcvits_amd import ops; ops.hubert_attention(...)`).  All
 tensors are float32 [B, C, T] on the GPU; nothing here records an autograd graph (the model is frozen).  There is no CPU
 fallback: CPU tensors raise."""
@@ -22,14 +28,34 @@ def _hb_gpu(t, what, dims=3):
     return t.detach().contiguous()
 
 
+def _hb_lengths(lengths, B, what):
+    if not isinstance(lengths, torch.Tensor) or not lengths.is_cuda:
+        raise RuntimeError("vcvits_amd: %s is not on the GPU; the HIP path has no CPU fallback" % what)
+    if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,):
+        raise ValueError("%s must be an int32 tensor of shape [%d] (one entry per batch row)" % (what, B))
+    return lengths.detach().contiguous()
+
+
 def hubert_attention_supported(B, H, head_dim, T):
     """True when the streamed attention kernel takes the shape (head_dim 64 or 80, B * H <= 65535, any T >= 1)."""
     return lib().vcv_hubert_attn_supported(int(B), int(H), int(head_dim), int(T)) == 0
 
 
-def hubert_attention(q, k, v, n_heads, scale=None):
+def _attn_launch(q, k, v, out, B, n_heads, d, T, ldb, scale, lengths):
+    scale = float(d) ** -0.5 if scale is None else float(scale)
+    if lengths is None:
+        check(lib().vcv_hubert_attn_fwd(q, k, v, ptr(out), B, n_heads, d, T, ldb, scale, stream()), "vcv_hubert_attn_fwd")
+    else:
+        check(lib().vcv_hubert_attn_fwd_len(q, k, v, ptr(out), B, n_heads, d, T, ldb, scale,
+                                            ptr(_hb_lengths(lengths, B, "lengths")), stream()), "vcv_hubert_attn_fwd_len")
+    return out
+
+
+def hubert_attention(q, k, v, n_heads, scale=None, lengths=None):
     """softmax((scale * q)^T k) v per head for q / k / v [B, n_heads * d, T] -> [B, n_heads * d, T]; scale defaults to
-    d ** -0.5.  Keys and values are streamed in tiles with a running max and sum (no [T, T] tensor)."""
+    d ** -0.5.  Keys and values are streamed in tiles with a running max and sum (no [T, T] tensor).  lengths (int32 [B] on
+    the GPU, entries in [1, T]): row b attends to the keys s < lengths[b] only, q / k / v at or behind lengths[b] are never
+    used, and the output there is exact 0."""
     q, k, v = _hb_gpu(q, "q"), _hb_gpu(k, "k"), _hb_gpu(v, "v")
     B, E, T = q.shape
     if k.shape != q.shape or v.shape != q.shape or E % n_heads:
@@ -38,13 +64,10 @@ def hubert_attention(q, k, v, n_heads, scale=None):
     if not hubert_attention_supported(B, n_heads, d, T):
         raise RuntimeError("vcvits_amd: hubert_attention has kernels for head dims %s and B * heads <= 65535; got "
                            "B=%d heads=%d head_dim=%d T=%d" % (HUBERT_HEAD_DIMS, B, n_heads, d, T))
-    out = torch.empty_like(q)
-    check(lib().vcv_hubert_attn_fwd(ptr(q), ptr(k), ptr(v), ptr(out), B, n_heads, d, T, E * T,
-                                    float(d) ** -0.5 if scale is None else float(scale), stream()), "vcv_hubert_attn_fwd")
-    return out
+    return _attn_launch(ptr(q), ptr(k), ptr(v), torch.empty_like(q), B, n_heads, d, T, E * T, scale, lengths)
 
 
-def hubert_attention_qkv(qkv, n_heads, scale=None):
+def hubert_attention_qkv(qkv, n_heads, scale=None, lengths=None):
     """hubert_attention over the output [B, 3 * n_heads * d, T] of one fused projection (q rows, then k, then v)."""
     qkv = _hb_gpu(qkv, "qkv")
     B, E3, T = qkv.shape
@@ -58,9 +81,7 @@ def hubert_attention_qkv(qkv, n_heads, scale=None):
     out = torch.empty((B, E, T), dtype=torch.float32, device=qkv.device)
     q = ptr(qkv)
     k, v = ctypes.c_void_p(q.value + 4 * E * T), ctypes.c_void_p(q.value + 8 * E * T)
-    check(lib().vcv_hubert_attn_fwd(q, k, v, ptr(out), B, n_heads, d, T, E3 * T,
-                                    float(d) ** -0.5 if scale is None else float(scale), stream()), "vcv_hubert_attn_fwd")
-    return out
+    return _attn_launch(q, k, v, out, B, n_heads, d, T, E3 * T, scale, lengths)
 
 
 def bias_gelu(x, bias=None, res=None, frames=None, inplace=False):
@@ -81,15 +102,33 @@ def bias_gelu(x, bias=None, res=None, frames=None, inplace=False):
     return y
 
 
-def groupnorm_gelu(x, weight, bias, eps=1e-5, inplace=False):
-    """gelu(F.group_norm(x, C, weight, bias, eps)) for x [B, C, T]: one group per channel, statistics over T in float64."""
+def groupnorm_gelu(x, weight, bias, eps=1e-5, inplace=False, lengths=None):
+    """gelu(F.group_norm(x, C, weight, bias, eps)) for x [B, C, T]: one group per channel, statistics over T in float64.
+    lengths (int32 [B] on the GPU, entries in [1, T]): the statistics of row b run over its first lengths[b] samples, samples
+    behind them are never read, and the output there is exact 0."""
     x, weight, bias = _hb_gpu(x, "x"), _hb_gpu(weight, "weight", 1), _hb_gpu(bias, "bias", 1)
     B, C, T = x.shape
     if weight.shape[0] != C or bias.shape[0] != C:
         raise ValueError("groupnorm_gelu: weight and bias must be [C]")
     y = x if inplace else torch.empty_like(x)
-    check(lib().vcv_hubert_groupnorm_gelu(ptr(x), ptr(weight), ptr(bias), ptr(y), B, C, T, eps, stream()),
-          "vcv_hubert_groupnorm_gelu")
+    if lengths is None:
+        check(lib().vcv_hubert_groupnorm_gelu(ptr(x), ptr(weight), ptr(bias), ptr(y), B, C, T, eps, stream()),
+              "vcv_hubert_groupnorm_gelu")
+    else:
+        check(lib().vcv_hubert_groupnorm_gelu_len(ptr(x), ptr(weight), ptr(bias), ptr(y), B, C, T,
+                                                  ptr(_hb_lengths(lengths, B, "lengths")), eps, stream()),
+              "vcv_hubert_groupnorm_gelu_len")
+    return y
+
+
+def mask_frames(x, lengths, inplace=False):
+    """x[b, c, t] where t < lengths[b], exact 0 elsewhere, for x [B, C, T] and lengths int32 [B] on the GPU.  A select: NaN
+    or Inf behind a row's end becomes 0, and valid frames keep their bits."""
+    x = _hb_gpu(x, "x")
+    B, C, T = x.shape
+    y = x if inplace else torch.empty_like(x)
+    check(lib().vcv_hubert_mask_frames(ptr(x), ptr(y), B, C, T, ptr(_hb_lengths(lengths, B, "lengths")), stream()),
+          "vcv_hubert_mask_frames")
     return y
 
 
