@@ -529,6 +529,16 @@ int vcv_rel_attn_bwd2(const float* q, const float* k, const float* v, const floa
                       const float* mask, const float* P, const float* out, const float* dO, float* dS, float* dq,
                       float* dk_out, float* dv, float* dembk, float* dembv, int B, int H, int dk, int T, int w, float qscale,
                       float pdrop, uint64_t seed, int bf16, void* stream);
+/* The forward pass of the same attention (relative_attention_transformer.py:150-182) with the keys and values STREAMED in
+ * tiles under a running max and sum: no dropout, no probability output, nothing of size T x T anywhere, so memory is linear
+ * in T and T has no upper limit.  What long-form inference runs.  q / k / v / out: [B, H*dk, T]; embk / embv: [2w+1, dk];
+ * mask: [B, T], a fill (a score is -1e4 where mask_i * mask_j == 0; a masked query row is uniform over all T keys), so
+ * masked values are still read.  Both contractions on the fp32 matrix cores in either compute mode.
+ * vcv_rel_attn_stream_supported() == 0 for the shapes the kernel takes (dk 32 or 64, 2w+1 <= 16, B*H <= 65535, T >= 1);
+ * the forward returns VCV_EINVAL for every other shape and for a null pointer, before any launch. */
+int vcv_rel_attn_stream_supported(int B, int H, int dk, int T, int w);
+int vcv_rel_attn_stream_fwd(const float* q, const float* k, const float* v, const float* embk, const float* embv,
+                            const float* mask, float* out, int B, int H, int dk, int T, int w, float qscale, void* stream);
 /* nn.Dropout (relative_attention_transformer.py:40,44,292): y = x * mask(seed, index) / (1-p); the
  * backward is the same call on dy with the same seed */
 int vcv_dropout(const float* x, float* y, int64_t n, float p, uint64_t seed, void* stream);

@@ -1,5 +1,9 @@
 """Microbenchmark of the fused attention kernels (forward + backward) at the content encoder's shapes.
-python tools/attn_bench.py [--dtype bf16] [--unfused] [--reps 20]"""
+python tools/attn_bench.py [--dtype bf16] [--unfused] [--reps 20]
+
+python tools/attn_bench.py --stream [--out profiles/attn_stream_bench.txt]: the no-grad forward without `attn`, the streamed
+kernel (attention_stream.hip) against the path that runs today at the same shape (VCVITS_ATTN_STREAM_MIN_T = 0), alternating
+in one process, three runs each, device events; median (min ... max), TFLOP/s as 4 B H T^2 dk / t, peak allocated bytes."""
 import argparse
 import os
 import sys
@@ -14,10 +18,81 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--dtype", default="f32")
 ap.add_argument("--unfused", action="store_true")
 ap.add_argument("--reps", type=int, default=20)
+ap.add_argument("--stream", action="store_true")
+ap.add_argument("--out", default=None)
 a = ap.parse_args()
 ops.set_compute_dtype(a.dtype)
 ops._ATTN_FUSED[0] = not a.unfused
 dev = torch.device("cuda:0")
+
+PEAK_F32_MFMA = 157.3  # TFLOP/s, v_mfma_f32_32x32x2_f32
+
+
+def stream_leg():
+    lines = ["# tools/attn_bench.py --stream --dtype %s: ops.rel_attention under no_grad, want_attn=False, ones mask, window 4." % a.dtype,
+             "# today = VCVITS_ATTN_STREAM_MIN_T=0 (fused workgroup-per-tile kernel at T <= 896, the three-launch path past it);",
+             "# streamed = VCVITS_ATTN_STREAM_MIN_T=1.  us per call: median (min ... max) of 3 runs, alternating, device events;",
+             "# TFLOP/s = 4 B H T^2 dk / median; of peak: against %.1f TFLOP/s of fp32 MFMA; peak MB: allocated over one call." % PEAK_F32_MFMA]
+    shapes = [(64, 4, 32, 500), (64, 4, 64, 500)]
+    shapes += [(B, 4, dk, T) for T in (1000, 4000, 15000) for B in (1, 8) for dk in (32, 64)]
+    old = ops._ATTN_STREAM_MIN_T[0]
+    try:
+        for B, H, dk, T in shapes:
+            t = lambda *s: torch.randn(*s, device=dev)
+            q, k, v = 2.0 * t(B, H * dk, T), t(B, H * dk, T), t(B, H * dk, T)
+            ek, ev = t(1, 9, dk) * dk ** -0.5, t(1, 9, dk) * dk ** -0.5
+            mask = torch.ones(B, T, device=dev)
+            flops = 4.0 * B * H * T * T * dk
+            # the three-launch path indexes its [B*H, T, T] tensors through int fields: not run past 2^31 elements
+            legs = [("streamed", 1)] + ([("today", 0)] if B * H * T * T < 2 ** 31 else [])
+            reps = max(2, min(10 * a.reps, int(4e12 / flops)))  # a timed window of tens of milliseconds at the least
+
+            def call(min_t):
+                ops._ATTN_STREAM_MIN_T[0] = min_t
+                with torch.no_grad():
+                    return ops.rel_attention(q, k, v, ek, ev, mask, H, 4, want_attn=False)[0]
+
+            outs, times, peaks = {}, {n: [] for n, _ in legs}, {}
+            for name, mt in legs:  # warm-up, peak memory of one call, and the outputs for the comparison
+                call(mt)
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.max_memory_allocated()
+                outs[name] = call(mt)
+                torch.cuda.synchronize()
+                peaks[name] = torch.cuda.max_memory_allocated() - base
+            for _ in range(3):
+                for name, mt in legs:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(reps):
+                        call(mt)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    times[name].append(e0.elapsed_time(e1) * 1e3 / reps)
+            diff = float((outs["streamed"] - outs["today"]).abs().max() / outs["today"].abs().max()) if "today" in outs else float("nan")
+            for name, _ in legs:
+                ts = sorted(times[name])
+                lines.append("B=%-2d H=%d dk=%-2d T=%-5d %-8s %10.1f us (%9.1f ... %9.1f) %6.2f TFLOP/s %5.3f of peak  peak %9.1f MB  reps %d" % (
+                    B, H, dk, T, name, ts[1], ts[0], ts[2], flops / ts[1] / 1e6, flops / ts[1] / 1e6 / PEAK_F32_MFMA, peaks[name] / 1e6, reps))
+            if "today" in outs:
+                lines.append("    streamed / today = %.3f of the time; max|streamed - today| / max|today| = %.1e" % (
+                    sorted(times["streamed"])[1] / sorted(times["today"])[1], diff))
+            else:
+                lines.append("    today: not run (B H T^2 = %.2e elements is past the int indexing of the three-launch path; 2 x %.1f GB)" % (
+                    B * H * T * T, B * H * T * T * 4 / 1e9))
+            print("\n".join(lines[-3:]), flush=True)
+            del outs
+    finally:
+        ops._ATTN_STREAM_MIN_T[0] = old
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if a.stream:
+    stream_leg()
+    sys.exit(0)
 for name, B, H, dk, T in (("base B16", 16, 4, 64, 204), ("base B32", 32, 4, 64, 204), ("48k B16", 16, 4, 32, 204), ("infer 48k", 64, 4, 32, 500)):
     t = lambda *s: torch.randn(*s, device=dev)
     q, k, v, gy = (t(B, H * dk, T).requires_grad_(True) for _ in range(4))

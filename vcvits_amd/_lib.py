@@ -111,6 +111,7 @@ EXPORTS = [
     "vcv_resample_table", "vcv_resample_apply", "vcv_phase_vocoder", "vcv_istft_ordered",
     "vcv_hubert_bias_gelu", "vcv_hubert_groupnorm_gelu", "vcv_hubert_layernorm_c_gelu", "vcv_hubert_attn_supported", "vcv_hubert_attn_fwd",
     "vcv_hubert_groupnorm_gelu_len", "vcv_hubert_mask_frames", "vcv_hubert_attn_fwd_len",
+    "vcv_rel_attn_stream_supported", "vcv_rel_attn_stream_fwd",
 ]
 
 
@@ -257,6 +258,8 @@ _ARGTYPES = {
     "vcv_hubert_groupnorm_gelu_len": [_P, _P, _P, _P, _I, _I, _I, _P, _F, _P],
     "vcv_hubert_mask_frames": [_P, _P, _I, _I, _I, _P, _P],
     "vcv_hubert_attn_fwd_len": [_P, _P, _P, _P, _I, _I, _I, _I, _L, _F, _P, _P],
+    "vcv_rel_attn_stream_supported": [_I, _I, _I, _I, _I],
+    "vcv_rel_attn_stream_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
 }
 
 

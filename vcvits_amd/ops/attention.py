@@ -134,6 +134,22 @@ class _RelAttnFusedFn(torch.autograd.Function):
 
 # the fused attention kernels (attention.hip) take every shape they support; VCVITS_ATTN_FUSED=0 keeps the unfused path
 _ATTN_FUSED = [tuning.flag("VCVITS_ATTN_FUSED", True, "relative-position attention as the fused MFMA kernels (0: the three-launch form)")]
+# the streamed forward (attention_stream.hip) takes the no-grad, no-dropout, no-`attn` calls from this T on; the default is
+# one frame past the fused kernels' longest T, so no call that reaches a fused kernel changes its bits
+_ATTN_STREAM_MIN_T = [tuning.integer("VCVITS_ATTN_STREAM_MIN_T", 897, "shortest T at which no-grad relative-position attention "
+                                     "runs on the streamed kernel (memory linear in T; 0: never)")]
+
+
+def _rel_attn_stream(q, k, v, embk, embv, mask, n_heads, window):
+    """One launch of vcv_rel_attn_stream_fwd: out [B, C, T], nothing of size T x T allocated."""
+    q, k, v, embk, embv, mask = (_f32c(t) for t in (q, k, v, embk, embv, mask))
+    B, C, T = q.shape
+    dk = C // n_heads
+    out = torch.empty_like(q)
+    check(lib().vcv_rel_attn_stream_fwd(ptr(q), ptr(k), ptr(v), ptr(embk), ptr(embv), ptr(mask), ptr(out), B, n_heads, dk, T,
+                                        window, 1.0 / (dk ** 0.5), stream()), "vcv_rel_attn_stream_fwd")
+    LAUNCH_COUNTS["attn_stream"] += 1
+    return out
 
 
 def rel_attention(q, k, v, emb_rel_k, emb_rel_v, mask, n_heads, window, pdrop=0.0, training=False, want_attn=True):
@@ -144,6 +160,10 @@ def rel_attention(q, k, v, emb_rel_k, emb_rel_v, mask, n_heads, window, pdrop=0.
     B, C, T = q.shape
     if p > 0 and DROPOUT_TRACE[0] is not None:
         DROPOUT_TRACE[0].append(("attn", p, seed, (B * n_heads, T, T)))
+    if (p == 0 and not want_attn and 0 < _ATTN_STREAM_MIN_T[0] <= T and
+            not (torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v, emb_rel_k, emb_rel_v))) and
+            lib().vcv_rel_attn_stream_supported(B, n_heads, C // n_heads, T, window) == 0):
+        return _rel_attn_stream(q, k, v, emb_rel_k, emb_rel_v, mask, n_heads, window), None
     if _ATTN_FUSED[0] and lib().vcv_rel_attn_supported(B, n_heads, C // n_heads, T, window) == 0:
         return _RelAttnFusedFn.apply(q, k, v, emb_rel_k, emb_rel_v, mask, n_heads, window, p, seed, bool(want_attn))
     return _RelAttnFn.apply(q, k, v, emb_rel_k, emb_rel_v, mask, n_heads, window, p, seed)
