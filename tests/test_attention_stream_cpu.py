@@ -67,26 +67,47 @@ def test_rows_restatement_equals_the_full_reference(case):
     assert r32.dtype == torch.float32 and A.dist(r32, some) <= 1e-5
 
 
-def test_stream_kernels_use_no_scratch_memory(tmp_path):
-    """`.private_segment_fixed_size: 0` for every kernel of attention_stream.hip, read from the built object (no GPU)."""
+def _kernel_notes(stem, tmp_path):
+    """{kernel name: {metadata field: int}} of the gfx950 code object inside csrc/<stem>.o."""
     from vcvits_amd import build_ext
-    build_ext.build(verbose=False)
     llvm = "/opt/rocm/lib/llvm/bin"
-    if not os.path.exists(os.path.join(llvm, "clang-offload-bundler")):
-        pytest.skip("no ROCm LLVM tools")
-    obj = os.path.join(build_ext.CSRC, "attention_stream.o")
-    fat, co = str(tmp_path / "a.fat"), str(tmp_path / "a.co")
+    obj = os.path.join(build_ext.CSRC, stem + ".o")
+    fat, co = str(tmp_path / (stem + ".fat")), str(tmp_path / (stem + ".co"))
     subprocess.run([os.path.join(llvm, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, obj], check=True)
     subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
                     "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
     notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
-    names = re.findall(r"\.name:\s+(\S*rel_attn_stream_fwd_kernel\S*)", notes)
-    sizes = [int(x) for x in re.findall(r"\.private_segment_fixed_size:\s+(\d+)", notes)]
-    spills = [int(x) for x in re.findall(r"\.vgpr_spill_count:\s+(\d+)", notes)]
-    lds = [int(x) for x in re.findall(r"\.group_segment_fixed_size:\s+(\d+)", notes)]
-    assert len(names) == 2 and len(sizes) >= 2, (names, sizes)   # dk = 32 and dk = 64 (and the helpers of common.h)
-    assert max(sizes) == 0 and max(spills) == 0, "a streamed attention kernel uses scratch: %s %s" % (sizes, spills)
-    assert max(lds) <= 64 * 1024, lds  # static LDS: no attribute call in the launcher
+    out = {}
+    for entry in re.split(r"\n\s+- \.", notes):  # one list item per kernel
+        name = re.search(r"\.?name:\s+(\S+)", entry)
+        if name and "private_segment_fixed_size" in entry:
+            out[name.group(1)] = {k: int(v) for k, v in re.findall(r"\.?(\w+):\s+(\d+)\s*$", entry, re.M)}
+    return out
+
+
+def test_stream_kernels_use_no_scratch_memory(tmp_path):
+    """The six instances that stand on csrc/attn_stream_tile.h, read from the built objects (no GPU): no scratch and no
+    spills anywhere in the two files, the static LDS of each instance, and the register budgets: at most 168 for the rel-pos
+    dk = 32 kernel (three workgroups of four waves per CU: 512 registers per SIMD lane / 3, in granules of 8), at most 256
+    (what one wave can address without spilling) for the others."""
+    from vcvits_amd import build_ext
+    build_ext.build(verbose=False)
+    if not os.path.exists("/opt/rocm/lib/llvm/bin/clang-offload-bundler"):
+        pytest.skip("no ROCm LLVM tools")
+    stream, hubert = _kernel_notes("attention_stream", tmp_path), _kernel_notes("hubert", tmp_path)
+    for name, f in list(stream.items()) + list(hubert.items()):
+        assert f["private_segment_fixed_size"] == 0 and f["vgpr_spill_count"] == 0 and f["sgpr_spill_count"] == 0, (name, f)
+        assert f["group_segment_fixed_size"] <= 64 * 1024, (name, f)  # static LDS: no attribute call in the launcher
+    want = {"rel_attn_stream_fwd_kernelILi32E": (30976, 168), "rel_attn_stream_fwd_kernelILi64E": (43392, 256),
+            "hubert_attn_fwd_kernelILi64ELb0E": (16640, 256), "hubert_attn_fwd_kernelILi64ELb1E": (16640, 256),
+            "hubert_attn_fwd_kernelILi80ELb0E": (22912, 256), "hubert_attn_fwd_kernelILi80ELb1E": (22912, 256)}
+    attn = {n: f for n, f in list(stream.items()) + list(hubert.items()) if "attn" in n}
+    assert len(attn) == 6, sorted(attn)
+    for key, (lds, regs) in want.items():
+        (name, f), = [(n, f) for n, f in attn.items() if key in n]
+        print(name, f)
+        assert f["group_segment_fixed_size"] == lds, (name, f)
+        assert f["vgpr_count"] <= regs, (name, f)  # unified count: vector and accumulation registers
 
 
 def test_entry_points_are_declared_and_check_their_arguments():

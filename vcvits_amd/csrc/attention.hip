@@ -104,9 +104,6 @@ constexpr int NTH = 64 * NWV;
 constexpr int RELP = 16;   // relative positions held per row (2w + 1 <= 16)
 constexpr int OP = 33;     // pitch of the partial-output tiles
 
-// row m of accumulator element e of lane half h (32x32 MFMA output layout; the lane's l31 is the column)
-__device__ __forceinline__ int acc_row(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
-
 // T1[32][TP] = alpha * A^T B for the 32 rows i0.. of A: T1[m][j] = alpha * sum_d A[d][i0 + m] * Bm[d][j]  (phase 1 of the
 // forward and of the backward row pass).  Key tiles are dealt to the NWV waves.
 template <bool BF>
@@ -474,10 +471,10 @@ __global__ void __launch_bounds__(NTH) rel_attn_bwd_cols_kernel(const AttnArgs p
 // latency and the matrix pipe ran 5-15 % of the time.  Here a wave owns its 32 queries from the first load to the output
 // store and never meets another wave after the prologue:
 //   * scores TRANSPOSED: S^T tile = K^T-tile (A: rows = keys) x Q (B: columns = queries), so in the accumulator layout a
-//     lane IS a query (column l31) and its registers are that query's keys (rows (e & 3) + 8 (e >> 2) + 4 h of tile jt):
+//     lane IS a query (column l31) and its registers are that query's keys (rows acc_row(e, h) of tile jt):
 //     the softmax is a reduction over the lane's own registers plus ONE exchange with lane ^ 32 -- no LDS, no barrier;
 //   * P V: O^T[d][i] = sum_j V[d][j] Pd[i][j] with B = the probability registers AS THEY ARE (reduction index of step s',
-//     half h := key (s' & 3) + 8 (s' >> 2) + 4 h of the tile -- any order of the reduction is fine as long as A uses the
+//     half h := key acc_row(s', h) of the tile -- any order of the reduction is fine as long as A uses the
 //     same one) and A = V read from an LDS image [d][j] of odd pitch (one conflict-free ds_read_b32 per MFMA); V is the
 //     only operand staged through LDS, once per workgroup of FW waves (the prologue's single barrier);
 //   * the two banded relative-position products ride on the matrix cores too, always in exact fp32
@@ -669,7 +666,7 @@ __global__ void __launch_bounds__(64 * FW) rel_attn_fwd_rows_kernel(const AttnAr
         const int r1 = jt * 32 + 4 * h - i + w + 1;  // 1 + relative position of key row 0
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const unsigned idx = (unsigned)(r1 + (e & 3) + 8 * (e >> 2));  // (negative: wraps, clamps to the zero slot at the end)
+          const unsigned idx = (unsigned)(r1 + acc_row(e, 0));  // (negative: wraps, clamps to the zero slot at the end)
           rv[e] = relw[l31 * RWP + (idx < (unsigned)(RWP - 1) ? idx : (unsigned)(RWP - 1))];
         }
       }
@@ -713,7 +710,7 @@ __global__ void __launch_bounds__(64 * FW) rel_attn_fwd_rows_kernel(const AttnAr
       static_for<0, NKT>([&](auto JT) {
         constexpr int jt = decltype(JT)::value;
 #pragma unroll
-        for (int e = 0; e < 16; ++e) ptile[l31 * PTP + (e & 3) + 8 * (e >> 2) + 4 * h] = acc[jt][e] * inv;
+        for (int e = 0; e < 16; ++e) ptile[l31 * PTP + acc_row(e, h)] = acc[jt][e] * inv;
         const int jj = jt * 32 + l31;
         float* drow = dst + ((size_t)g * T + it * 32 + h) * T + jj;
 #pragma unroll
@@ -731,7 +728,7 @@ __global__ void __launch_bounds__(64 * FW) rel_attn_fwd_rows_kernel(const AttnAr
       static_for<0, NKT>([&](auto JT) {
         constexpr int jt = decltype(JT)::value;
 #pragma unroll
-        for (int e = 0; e < 16; ++e) acc[jt][e] *= drop_scale(seed, rowoff + jt * 32 + (e & 3) + 8 * (e >> 2), p.pdrop, inv_keep);
+        for (int e = 0; e < 16; ++e) acc[jt][e] *= drop_scale(seed, rowoff + jt * 32 + acc_row(e, 0), p.pdrop, inv_keep);
       });
     }
     if (p.Pd) store_tiles(p.Pd);
@@ -747,7 +744,7 @@ __global__ void __launch_bounds__(64 * FW) rel_attn_fwd_rows_kernel(const AttnAr
         const int r1 = jt * 32 + 4 * h - i + w + 1;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const unsigned idx = (unsigned)(r1 + (e & 3) + 8 * (e >> 2));
+          const unsigned idx = (unsigned)(r1 + acc_row(e, 0));
           relw[l31 * RWP + (idx < (unsigned)(RWP - 1) ? idx : (unsigned)(RWP - 1))] = acc[jt][e];
         }
       }
@@ -776,7 +773,7 @@ __global__ void __launch_bounds__(64 * FW) rel_attn_fwd_rows_kernel(const AttnAr
 #pragma unroll
               for (int e = 0; e < 8; ++e) {
                 const int s2 = 8 * m2 + e;
-                afr[e] = (__bf16)Vl[32 * t * TPV + jt * 32 + (s2 & 3) + 8 * (s2 >> 2)];
+                afr[e] = (__bf16)Vl[32 * t * TPV + jt * 32 + acc_row(s2, 0)];
               }
               oacc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr, bfr, oacc[t], 0, 0, 0);
             }
@@ -786,7 +783,7 @@ __global__ void __launch_bounds__(64 * FW) rel_attn_fwd_rows_kernel(const AttnAr
           for (int s2 = 0; s2 < 16; ++s2) {
 #pragma unroll
             for (int t = 0; t < NT; ++t)
-              oacc[t] = mma32(Vl[32 * t * TPV + jt * 32 + (s2 & 3) + 8 * (s2 >> 2)], acc[jt][s2], oacc[t]);
+              oacc[t] = mma32(Vl[32 * t * TPV + jt * 32 + acc_row(s2, 0)], acc[jt][s2], oacc[t]);
           }
         }
       }
@@ -970,7 +967,7 @@ __global__ void __launch_bounds__(64 * FW) rel_attn_bwd_rows2_kernel(const AttnA
       if (near) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const unsigned idx = (unsigned)(r1 + (e & 3) + 8 * (e >> 2));
+          const unsigned idx = (unsigned)(r1 + acc_row(e, 0));
           rv[e] = relw[l31 * RWP + (idx < (unsigned)(RWP - 1) ? idx : (unsigned)(RWP - 1))];
         }
       }
@@ -982,7 +979,7 @@ __global__ void __launch_bounds__(64 * FW) rel_attn_bwd_rows2_kernel(const AttnA
       for (int e = 0; e < 16; ++e) cd[e] = 1.f;
       if (p.pdrop > 0.f) {
 #pragma unroll
-        for (int e = 0; e < 16; ++e) cd[e] = drop_scale(p.seed + (p.seed_off ? *p.seed_off : 0ull), rowoff + jt * 32 + (e & 3) + 8 * (e >> 2), p.pdrop, inv_keep);
+        for (int e = 0; e < 16; ++e) cd[e] = drop_scale(p.seed + (p.seed_off ? *p.seed_off : 0ull), rowoff + jt * 32 + acc_row(e, 0), p.pdrop, inv_keep);
       }
       unsigned wl = 0;
       if constexpr (masked) {
@@ -992,17 +989,17 @@ __global__ void __launch_bounds__(64 * FW) rel_attn_bwd_rows2_kernel(const AttnA
       float pd[16], dsv[16];
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const float pv = ptile[l31 * PTP + (e & 3) + 8 * (e >> 2) + 4 * h];
+        const float pv = ptile[l31 * PTP + acc_row(e, h)];
         const float dpc = (acc[jt][e] + rv[e]) * cd[e];
         float ds = pv * (dpc - dot);
-        if constexpr (masked) ds = (wl & (1u << ((e & 3) + 8 * (e >> 2)))) ? ds : 0.f;
+        if constexpr (masked) ds = (wl & (1u << acc_row(e, 0))) ? ds : 0.f;
         pd[e] = pv * cd[e];
         dsv[e] = ds;
       }
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         acc[jt][e] = dsv[e];
-        ptile[l31 * PTP + (e & 3) + 8 * (e >> 2) + 4 * h] = dsv[e];
+        ptile[l31 * PTP + acc_row(e, h)] = dsv[e];
       }
       const int jj = jt * 32 + l31;
       float* drow = p.dS + ((size_t)g * T + it * 32 + h) * T + jj;
@@ -1014,7 +1011,7 @@ __global__ void __launch_bounds__(64 * FW) rel_attn_bwd_rows2_kernel(const AttnA
       if (near) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const unsigned idx = (unsigned)(r1 + (e & 3) + 8 * (e >> 2));
+          const unsigned idx = (unsigned)(r1 + acc_row(e, 0));
           const unsigned ic = idx < (unsigned)(RWP - 1) ? idx : (unsigned)(RWP - 1);
           relp[l31 * RWP + ic] = pd[e];
           rels[l31 * RWP + ic] = dsv[e];
@@ -1045,7 +1042,7 @@ __global__ void __launch_bounds__(64 * FW) rel_attn_bwd_rows2_kernel(const AttnA
 #pragma unroll
               for (int e = 0; e < 8; ++e) {
                 const int s2 = 8 * m2 + e;
-                afr[e] = (__bf16)Kr[32 * t * TPV + jt * 32 + (s2 & 3) + 8 * (s2 >> 2)];
+                afr[e] = (__bf16)Kr[32 * t * TPV + jt * 32 + acc_row(s2, 0)];
               }
               oacc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr, bfr, oacc[t], 0, 0, 0);
             }
@@ -1055,7 +1052,7 @@ __global__ void __launch_bounds__(64 * FW) rel_attn_bwd_rows2_kernel(const AttnA
           for (int s2 = 0; s2 < 16; ++s2) {
 #pragma unroll
             for (int t = 0; t < NT; ++t)
-              oacc[t] = mma32(Kr[32 * t * TPV + jt * 32 + (s2 & 3) + 8 * (s2 >> 2)], acc[jt][s2], oacc[t]);
+              oacc[t] = mma32(Kr[32 * t * TPV + jt * 32 + acc_row(s2, 0)], acc[jt][s2], oacc[t]);
           }
         }
       }
@@ -1157,9 +1154,9 @@ __global__ void __launch_bounds__(64 * FW) rel_attn_bwd_cols2_kernel(const AttnA
   auto load_tiles = [&](float (&pq)[16], float (&dq_)[16], int it) __attribute__((always_inline)) {
     const unsigned roff = joff + (unsigned)(it * 32 + 4 * h) * lp.T4;  // (a row past T lands past the matrix: 0)
 #pragma unroll
-    for (int e = 0; e < 16; ++e) pq[e] = lp(roff, (e & 3) + 8 * (e >> 2));
+    for (int e = 0; e < 16; ++e) pq[e] = lp(roff, acc_row(e, 0));
 #pragma unroll
-    for (int e = 0; e < 16; ++e) dq_[e] = ls(roff, (e & 3) + 8 * (e >> 2));
+    for (int e = 0; e < 16; ++e) dq_[e] = ls(roff, acc_row(e, 0));
   };
   load_tiles(pv[0], ds[0], 0);
   static_for<0, NKT>([&](auto IT) {
@@ -1171,7 +1168,7 @@ __global__ void __launch_bounds__(64 * FW) rel_attn_bwd_cols2_kernel(const AttnA
       if (p.pdrop > 0.f) {
 #pragma unroll
         for (int e = 0; e < 16; ++e)
-          pc[e] *= drop_scale(p.seed + (p.seed_off ? *p.seed_off : 0ull), ((size_t)g * T + it * 32 + 4 * h + (e & 3) + 8 * (e >> 2)) * T + j, p.pdrop, inv_keep);
+          pc[e] *= drop_scale(p.seed + (p.seed_off ? *p.seed_off : 0ull), ((size_t)g * T + it * 32 + 4 * h + acc_row(e, 0)) * T + j, p.pdrop, inv_keep);
       }
       if constexpr (BF) {
 #pragma unroll
@@ -1184,7 +1181,7 @@ __global__ void __launch_bounds__(64 * FW) rel_attn_bwd_cols2_kernel(const AttnA
             bf16x8 ao, aq;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-              const int s2 = 8 * m2 + e, off = 32 * t * TPV + it * 32 + (s2 & 3) + 8 * (s2 >> 2);
+              const int s2 = 8 * m2 + e, off = 32 * t * TPV + it * 32 + acc_row(s2, 0);
               ao[e] = (__bf16)Ol[off], aq[e] = (__bf16)Ql[off];
             }
             av[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ao, bp, av[t], 0, 0, 0);
@@ -1196,7 +1193,7 @@ __global__ void __launch_bounds__(64 * FW) rel_attn_bwd_cols2_kernel(const AttnA
         for (int s2 = 0; s2 < 16; ++s2) {
 #pragma unroll
           for (int t = 0; t < NT; ++t) {
-            const int off = 32 * t * TPV + it * 32 + (s2 & 3) + 8 * (s2 >> 2);
+            const int off = 32 * t * TPV + it * 32 + acc_row(s2, 0);
             av[t] = mma32(Ol[off], pc[s2], av[t]);
             ak[t] = mma32(Ql[off], dc[s2], ak[t]);
           }

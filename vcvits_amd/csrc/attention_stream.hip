@@ -2,13 +2,9 @@
 // (vits/model/transformer/relative_attention_transformer.py:150-182), forward only, no dropout, no probability output:
 // what long-form inference runs.  Nothing of size T x T exists, so memory is linear in T and T is not bounded by LDS.
 //
-// The frame is hubert_attn_fwd_kernel (hubert.hip): a block is one head and 128 queries, each of its 4 waves owns 32
-// queries for the whole launch, the block streams keys / values in tiles of 32 through LDS, and both contractions run on
-// v_mfma_f32_32x32x2_f32 (exact fp32 products, whatever the compute mode):
-//   S^T[s][t] = sum_d K[d][s] Q[d][t]   A = K tile from LDS, B = this lane's query column (pre-scaled) in registers;
-//   O[d][t]  += sum_s V[d][s] P^T[s][t]  A = V tile from LDS, B = the S^T accumulator itself.
-// A lane is a query (lane & 31) and holds 16 of the tile's 32 keys (the other 16 in lane ^ 32): register r is key
-// (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) of the tile.  On top of that frame, following tests/attention_f64.py points 1, 2, 4:
+// The frame -- block, tiles of 32 keys, the two MFMA contractions, which key a lane's register holds -- is the one of
+// attn_stream_tile.h, shared with hubert_attn_fwd_kernel (hubert.hip); this kernel takes it with __expf.  What is this
+// kernel's own, following tests/attention_f64.py points 1, 2, 4:
 //   * fill: a score is -1e4 by SELECT where mask_i * mask_j == 0 (the tile's 32 mask values are staged beside the keys).
 //     A masked query is uniform over all T keys; a wholly masked first tile starts the running max at -1e4 and the first
 //     real score rescales it away (alpha = exp(-1e4 - max) = 0).  No tile is skipped.  Keys at or past T are -inf.
@@ -21,12 +17,11 @@
 //     as the output accumulator is rescaled; at the end out += sum_r pb[r] * carry * embv[r] and everything is scaled by 1 / l.
 // Every index that scales with T is size_t.  Grid (ceil(T / 128), B * H), 256 threads.
 //
-// Resources (hipcc -O3, gfx950, from the code object's metadata; tests/test_attention_stream_cpu.py reads the scratch size):
-//   dk = 32: 164 registers (16 of them accumulation registers), 61 SGPR, 30,976 B LDS, 0 B scratch, no spills;
-//   dk = 64: 240 registers (32 of them accumulation registers), 61 SGPR, 43,392 B LDS, 0 B scratch, no spills.
-// So two (dk = 64) or three (dk = 32) workgroups share a CU.
-#include "common.h"
-#include <math.h>
+// Resources (hipcc -O3, gfx950, from the code object's metadata; tests/test_attention_stream_cpu.py holds them):
+//   dk = 32: 168 registers (16 of them accumulation registers), 57 SGPR, 30,976 B LDS, 0 B scratch, no spills;
+//   dk = 64: 244 registers (32 of them accumulation registers), 57 SGPR, 43,392 B LDS, 0 B scratch, no spills.
+// So two (dk = 64) or three (dk = 32) workgroups share a CU; 168 is the last register count at which three do.
+#include "attn_stream_tile.h"
 
 namespace {
 
@@ -39,9 +34,8 @@ rel_attn_stream_fwd_kernel(const float* __restrict__ q, const float* __restrict_
                            const float* __restrict__ embk, const float* __restrict__ embv, const float* __restrict__ mask,
                            float* __restrict__ out, int H, int T, int w, float qscale) {
   constexpr int DT = D / 32;  // output tiles of 32 channels
-  constexpr int VS = 33;      // row stride of the value tile: its A fragments walk d across lanes
   __shared__ float Ks[D * 32];
-  __shared__ float Vs[D * VS];
+  __shared__ float Vs[D * TILE_VS];
   __shared__ __attribute__((aligned(16))) float Ms[32];
   __shared__ float Ek[RELS * D];
   __shared__ float Ev[RELS * D];
@@ -58,8 +52,7 @@ rel_attn_stream_fwd_kernel(const float* __restrict__ q, const float* __restrict_
   const int row = (wv * 32 + col) * RS;
 
   float qr[D / 2];
-#pragma unroll
-  for (int i = 0; i < D / 2; ++i) qr[i] = tok ? q[base + (size_t)(2 * i + hf) * T + t] * qscale : 0.f;
+  tile_load_q<D>(qr, q, base, T, t, hf, qscale, tok);
   const float mi = tok ? mask[mbase + t] : 0.f;
   for (int i = tid; i < RELS * D; i += 256) {
     Ek[i] = i < nr * D ? embk[i] : 0.f;
@@ -76,49 +69,28 @@ rel_attn_stream_fwd_kernel(const float* __restrict__ q, const float* __restrict_
     if (hf == 0) Rl[row + r] = a;
   }
 
-  f32x16 o[DT];
-#pragma unroll
-  for (int j = 0; j < DT; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[j][r] = 0.f;
+  f32x16 o[DT] = {};
   float m = -INFINITY, l = 0.f;
   float c0 = 0.f, c1 = 0.f, c2 = 0.f;  // rescale carried by the band entries of the tiles at t0 - 32, t0, t0 + 32
 
-  const int sd = tid >> 5, sc = tid & 31;
   for (int s0 = 0; s0 < T; s0 += 32) {
     __syncthreads();  // the previous tile has been read (first pass: Rl is written)
-    {
-      const int s = s0 + sc;
-      const bool sok = s < T;
-#pragma unroll
-      for (int i = 0; i < D / 8; ++i) {
-        const int d = sd + 8 * i;
-        const size_t g = base + (size_t)d * T + (sok ? s : 0);
-        Ks[d * 32 + sc] = sok ? k[g] : 0.f;
-        Vs[d * VS + sc] = sok ? v[g] : 0.f;
-      }
-      if (tid < 32) Ms[sc] = sok ? mask[mbase + s] : 0.f;
-    }
+    tile_stage_kv<D>(Ks, Vs, k, v, base, T, s0, T, tid);
+    if (tid < 32) Ms[tid] = s0 + tid < T ? mask[mbase + s0 + tid] : 0.f;
     __syncthreads();
-
-    f32x16 S;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) S[r] = 0.f;
-#pragma unroll
-    for (int i = 0; i < D / 2; ++i) S = __builtin_amdgcn_mfma_f32_32x32x2f32(Ks[(2 * i + hf) * 32 + col], qr[i], S, 0, 0, 0);
+    f32x16 S = tile_scores<D>(Ks, qr, col, hf);
 
     const int ds = s0 - t0;
     const bool band = ds >= -32 && ds <= 32;  // wave-uniform
     if (band) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int off = ds + (r & 3) + 8 * (r >> 2) + 4 * hf - col + w;  // key - query + w
+        const int off = ds + acc_row(r, hf) - col + w;  // key - query + w
         const bool inb = off >= 0 && off < nr;
         const float rel = Rl[row + (inb ? off : 0)];
         S[r] += inb ? rel : 0.f;
       }
     }
-    float mx = -INFINITY;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const float4 mj = *reinterpret_cast<const float4*>(&Ms[8 * g + 4 * hf]);
@@ -130,22 +102,10 @@ rel_attn_stream_fwd_kernel(const float* __restrict__ q, const float* __restrict_
     if (s0 + 32 > T) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        if (s0 + (r & 3) + 8 * (r >> 2) + 4 * hf >= T) S[r] = -INFINITY;
+        if (s0 + acc_row(r, hf) >= T) S[r] = -INFINITY;
     }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, S[r]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float mn = fmaxf(m, mx);  // finite from the first tile on: key 0 exists and is -1e4 at the least
-    const float alpha = __expf(m - mn);
-    float rs = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      S[r] = __expf(S[r] - mn);
-      rs += S[r];
-    }
-    rs += __shfl_xor(rs, 32);
-    l = l * alpha + rs;
-    m = mn;
+    // the new max is finite from the first tile on: key 0 exists and is -1e4 at the least
+    const float alpha = tile_softmax_step<true>(S, m, l);
     c0 *= alpha, c1 *= alpha, c2 *= alpha;
     if (band) {
       if (ds < 0) c0 = 1.f;
@@ -153,20 +113,12 @@ rel_attn_stream_fwd_kernel(const float* __restrict__ q, const float* __restrict_
       else c2 = 1.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int sr = (r & 3) + 8 * (r >> 2) + 4 * hf;
+        const int sr = acc_row(r, hf);
         const int off = ds + sr - col + w;
         if (off >= 0 && off < nr && s0 + sr < T) Pb[row + off] = S[r];
       }
     }
-#pragma unroll
-    for (int j = 0; j < DT; ++j) o[j] *= alpha;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int sr = (r & 3) + 8 * (r >> 2) + 4 * hf;
-#pragma unroll
-      for (int j = 0; j < DT; ++j)
-        o[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(Vs[(j * 32 + col) * VS + sr], S[r], o[j], 0, 0, 0);
-    }
+    tile_pv(o, Vs, S, alpha, col, hf);
   }
 
   __syncthreads();  // both lanes of a query read the band entries either of them wrote
@@ -178,16 +130,9 @@ rel_attn_stream_fwd_kernel(const float* __restrict__ q, const float* __restrict_
 #pragma unroll
     for (int j = 0; j < DT; ++j)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) o[j][e] += p * Ev[r * D + j * 32 + (e & 3) + 8 * (e >> 2) + 4 * hf];
+      for (int e = 0; e < 16; ++e) o[j][e] += p * Ev[r * D + j * 32 + acc_row(e, hf)];
   }
-  const float inv = 1.f / l;
-#pragma unroll
-  for (int j = 0; j < DT; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int d = j * 32 + (r & 3) + 8 * (r >> 2) + 4 * hf;
-      out[base + (size_t)d * T + t] = o[j][r] * inv;
-    }
+  tile_store<D>(out, base, T, t, o, l, hf, true);
 }
 
 }  // namespace

@@ -9,6 +9,9 @@
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// 32x32 MFMA output layout: accumulator element e of lane half h (lane >> 5) is row acc_row(e, h); lane & 31 is the column
+__device__ __forceinline__ int acc_row(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
+
 #define VCV_LDS_LIMIT (160 * 1024)
 
 __device__ __forceinline__ float vcv_leaky(float v, float s) { return v > 0.f ? v : v * s; }

@@ -1,5 +1,6 @@
 // hubert.hip -- what HuBERT inference (vcvits_amd/model/hubert.py) needs beyond the conv family and layernorm_c:
-//   * softmax self-attention, forward only, keys / values streamed in tiles (no [T, T] tensor in memory);
+//   * softmax self-attention, forward only, keys / values streamed in tiles (no [T, T] tensor in memory), on the frame of
+//     attn_stream_tile.h that the streamed relative-position kernel (attention_stream.hip) shares;
 //   * GroupNorm(C, C) over time fused with GELU (layer 0 of the base model's conv front end);
 //   * LayerNorm over channels fused with GELU (every layer of the large models' front end);
 //   * bias + exact GELU (+ residual) as one streaming pass.
@@ -14,8 +15,7 @@
 //   * vcv_hubert_attn_fwd_len        keys s < frames[b] only, exact 0 for the queries behind them.
 // All three select, never multiply: NaN or Inf behind a row's end does not reach a valid frame.  The entry points without
 // lengths are the same kernels instantiated without the array, with the instructions they had before it existed.
-#include "common.h"
-#include <math.h>
+#include "attn_stream_tile.h"
 
 namespace {
 
@@ -149,16 +149,10 @@ hubert_layernorm_c_gelu_kernel(const float* x, const float* __restrict__ gamma, 
   }
 }
 
-// ---- softmax((q * scale)^T k) v per head, forward only.  q / k / v / out: [B, H * D, T], i.e. a head is D rows of T; batch
-// rows of q / k / v are `ldb` floats apart (H * D * T, or 3 * H * D * T when the three are slices of one fused projection).
-// A block is one head and 128 queries: each of its 4 waves owns 32 queries for the whole launch and the block streams the
-// keys / values in tiles of 32 through LDS.  Both contractions run on v_mfma_f32_32x32x2_f32 (exact fp32 products):
-//   S^T[s][t] = sum_d K[d][s] Q[d][t]   A = K tile from LDS, B = this lane's query column held in registers for the launch;
-//   O[d][t]  += sum_s V[d][s] P^T[s][t]  A = V tile from LDS, B = the S^T accumulator itself.
-// S^T leaves the matrix pipe with the query on the lane and 16 of the tile's 32 keys in the lane's registers (the other 16
-// in lane ^ 32), so the running max / sum of a query is a loop over registers plus one cross-lane exchange, and register r
-// is already the B operand of the k-pair {row(r, half 0), row(r, half 1)} of the second product: no LDS round trip for P,
-// nothing of size T x T anywhere.  D = 80 pads the value tile to 96 rows of zeros (3 output tiles of 32 channels).
+// ---- softmax((q * scale)^T k) v per head, forward only, on the streamed frame of attn_stream_tile.h (layout, tiles and
+// the two MFMA contractions are described there), with expf.  q / k / v / out: [B, H * D, T]; batch rows of q / k / v are
+// `ldb` floats apart (H * D * T, or 3 * H * D * T when the three are slices of one fused projection).  Grid
+// (ceil(T / 128), B * H), 256 threads.  D = 80 pads the value tile to 96 rows of zeros (3 output tiles of 32 channels).
 // LEN: a head of batch row b sees the keys s < n = frames[b] only (precondition 1 <= frames[b] <= T, so key 0 exists; the
 // value is clamped into that range, so a bad one cannot read out of bounds).  The key loop ends at n, keys / values and
 // queries at or behind n are staged as 0 by a select (whatever is stored there, NaN included, is never used), their scores
@@ -169,9 +163,8 @@ __global__ void __launch_bounds__(256)
 hubert_attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                        float* __restrict__ out, int H, int T, size_t ldb, float scale, const int* __restrict__ frames) {
   constexpr int DT = (D + 31) / 32;  // output tiles of 32 channels
-  constexpr int VS = 33;             // row stride of the value tile: its A fragments walk d across lanes
   __shared__ float Ks[D * 32];
-  __shared__ float Vs[DT * 32 * VS];
+  __shared__ float Vs[DT * 32 * TILE_VS];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int col = lane & 31, hf = lane >> 5;
   const size_t base = (size_t)(blockIdx.y / H) * ldb + (size_t)(blockIdx.y % H) * D * T;
@@ -191,78 +184,24 @@ hubert_attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
   const bool qok = t < n;
 
   float qr[D / 2];
-#pragma unroll
-  for (int i = 0; i < D / 2; ++i) qr[i] = qok ? q[base + (size_t)(2 * i + hf) * T + t] * scale : 0.f;
-  for (int i = D * VS + tid; i < DT * 32 * VS; i += 256) Vs[i] = 0.f;
-
-  f32x16 o[DT];
-#pragma unroll
-  for (int j = 0; j < DT; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[j][r] = 0.f;
+  tile_load_q<D>(qr, q, base, T, t, hf, scale, qok);
+  for (int i = D * TILE_VS + tid; i < DT * 32 * TILE_VS; i += 256) Vs[i] = 0.f;
+  f32x16 o[DT] = {};
   float m = -INFINITY, l = 0.f;
 
-  const int sd = tid >> 5, sc = tid & 31;
   for (int s0 = 0; s0 < n; s0 += 32) {
     __syncthreads();  // the previous tile has been read
-    {
-      const int s = s0 + sc;
-      const bool sok = s < n;
-#pragma unroll
-      for (int i = 0; i < D / 8; ++i) {
-        const int d = sd + 8 * i;
-        const size_t g = base + (size_t)d * T + (sok ? s : 0);
-        Ks[d * 32 + sc] = sok ? k[g] : 0.f;
-        Vs[d * VS + sc] = sok ? v[g] : 0.f;
-      }
-    }
+    tile_stage_kv<D>(Ks, Vs, k, v, base, T, s0, n, tid);
     __syncthreads();
-
-    f32x16 S;
+    f32x16 S = tile_scores<D>(Ks, qr, col, hf);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) S[r] = 0.f;
-#pragma unroll
-    for (int i = 0; i < D / 2; ++i) S = __builtin_amdgcn_mfma_f32_32x32x2f32(Ks[(2 * i + hf) * 32 + col], qr[i], S, 0, 0, 0);
-
-    float mx = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int s = s0 + (r & 3) + 8 * (r >> 2) + 4 * hf;
-      if (s >= n) S[r] = -INFINITY;
-      mx = fmaxf(mx, S[r]);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float mn = fmaxf(m, mx);  // finite from the first tile on: key 0 exists
-    const float alpha = expf(m - mn);
-    float rs = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      S[r] = expf(S[r] - mn);
-      rs += S[r];
-    }
-    rs += __shfl_xor(rs, 32);
-    l = l * alpha + rs;
-    m = mn;
-#pragma unroll
-    for (int j = 0; j < DT; ++j) o[j] *= alpha;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int sr = (r & 3) + 8 * (r >> 2) + 4 * hf;
-#pragma unroll
-      for (int j = 0; j < DT; ++j)
-        o[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(Vs[(j * 32 + col) * VS + sr], S[r], o[j], 0, 0, 0);
-    }
+    for (int r = 0; r < 16; ++r)
+      if (s0 + acc_row(r, hf) >= n) S[r] = -INFINITY;
+    const float alpha = tile_softmax_step<false>(S, m, l);
+    tile_pv(o, Vs, S, alpha, col, hf);
   }
 
-  if (!tok) return;
-  const float inv = 1.f / l;
-#pragma unroll
-  for (int j = 0; j < DT; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int d = j * 32 + (r & 3) + 8 * (r >> 2) + 4 * hf;
-      if (d < D) out[obase + (size_t)d * T + t] = (!LEN || qok) ? o[j][r] * inv : 0.f;
-    }
+  if (tok) tile_store<D>(out, obase, T, t, o, l, hf, !LEN || qok);
 }
 
 }  // namespace
@@ -277,22 +216,25 @@ extern "C" int vcv_hubert_bias_gelu(const float* x, const float* bias, const flo
   return vcv_check_launch();
 }
 
-extern "C" int vcv_hubert_groupnorm_gelu(const float* x, const float* gamma, const float* beta, float* y, int B, int C, int T,
-                                         float eps, void* stream) {
+// counts: null launches the kernel without lengths
+static int groupnorm_gelu_launch(const float* x, const float* gamma, const float* beta, float* y, int B, int C, int T,
+                                 const int* counts, float eps, void* stream) {
   if (!x || !gamma || !beta || !y || B <= 0 || C <= 0 || T <= 0) return VCV_EINVAL;
   const long long rows = (long long)B * C;
   if (rows > 0x7fffffffLL) return VCV_EINVAL;
-  hubert_groupnorm_gelu_kernel<false><<<(unsigned)rows, 256, 0, (hipStream_t)stream>>>(x, gamma, beta, y, C, T, eps, nullptr);
+  const auto kernel = counts ? hubert_groupnorm_gelu_kernel<true> : hubert_groupnorm_gelu_kernel<false>;
+  kernel<<<(unsigned)rows, 256, 0, (hipStream_t)stream>>>(x, gamma, beta, y, C, T, eps, counts);
   return vcv_check_launch();
+}
+
+extern "C" int vcv_hubert_groupnorm_gelu(const float* x, const float* gamma, const float* beta, float* y, int B, int C, int T,
+                                         float eps, void* stream) {
+  return groupnorm_gelu_launch(x, gamma, beta, y, B, C, T, nullptr, eps, stream);
 }
 
 extern "C" int vcv_hubert_groupnorm_gelu_len(const float* x, const float* gamma, const float* beta, float* y, int B, int C,
                                              int T, const int* counts, float eps, void* stream) {
-  if (!x || !gamma || !beta || !y || !counts || B <= 0 || C <= 0 || T <= 0) return VCV_EINVAL;
-  const long long rows = (long long)B * C;
-  if (rows > 0x7fffffffLL) return VCV_EINVAL;
-  hubert_groupnorm_gelu_kernel<true><<<(unsigned)rows, 256, 0, (hipStream_t)stream>>>(x, gamma, beta, y, C, T, eps, counts);
-  return vcv_check_launch();
+  return counts ? groupnorm_gelu_launch(x, gamma, beta, y, B, C, T, counts, eps, stream) : VCV_EINVAL;
 }
 
 extern "C" int vcv_hubert_mask_frames(const float* x, float* y, int B, int C, int T, const int* frames, void* stream) {
@@ -316,25 +258,22 @@ extern "C" int vcv_hubert_attn_supported(int B, int H, int dk, int T) {
   return (dk == 64 || dk == 80) ? 0 : 1;
 }
 
+// frames: null launches the kernel without lengths
+static int attn_fwd_launch(const float* q, const float* k, const float* v, float* out, int B, int H, int dk, int T,
+                           int64_t ldb, float scale, const int* frames, void* stream) {
+  if (!q || !k || !v || !out || vcv_hubert_attn_supported(B, H, dk, T) != 0 || ldb < (int64_t)H * dk * T) return VCV_EINVAL;
+  const auto kernel = dk == 64 ? (frames ? hubert_attn_fwd_kernel<64, true> : hubert_attn_fwd_kernel<64, false>)
+                               : (frames ? hubert_attn_fwd_kernel<80, true> : hubert_attn_fwd_kernel<80, false>);
+  kernel<<<dim3(vcv_cdiv(T, 128), B * H), 256, 0, (hipStream_t)stream>>>(q, k, v, out, H, T, (size_t)ldb, scale, frames);
+  return vcv_check_launch();
+}
+
 extern "C" int vcv_hubert_attn_fwd(const float* q, const float* k, const float* v, float* out, int B, int H, int dk, int T,
                                    int64_t ldb, float scale, void* stream) {
-  if (!q || !k || !v || !out || vcv_hubert_attn_supported(B, H, dk, T) != 0 || ldb < (int64_t)H * dk * T) return VCV_EINVAL;
-  const dim3 grid(vcv_cdiv(T, 128), B * H);
-  if (dk == 64)
-    hubert_attn_fwd_kernel<64, false><<<grid, 256, 0, (hipStream_t)stream>>>(q, k, v, out, H, T, (size_t)ldb, scale, nullptr);
-  else
-    hubert_attn_fwd_kernel<80, false><<<grid, 256, 0, (hipStream_t)stream>>>(q, k, v, out, H, T, (size_t)ldb, scale, nullptr);
-  return vcv_check_launch();
+  return attn_fwd_launch(q, k, v, out, B, H, dk, T, ldb, scale, nullptr, stream);
 }
 
 extern "C" int vcv_hubert_attn_fwd_len(const float* q, const float* k, const float* v, float* out, int B, int H, int dk, int T,
                                        int64_t ldb, float scale, const int* frames, void* stream) {
-  if (!q || !k || !v || !out || !frames || vcv_hubert_attn_supported(B, H, dk, T) != 0 || ldb < (int64_t)H * dk * T)
-    return VCV_EINVAL;
-  const dim3 grid(vcv_cdiv(T, 128), B * H);
-  if (dk == 64)
-    hubert_attn_fwd_kernel<64, true><<<grid, 256, 0, (hipStream_t)stream>>>(q, k, v, out, H, T, (size_t)ldb, scale, frames);
-  else
-    hubert_attn_fwd_kernel<80, true><<<grid, 256, 0, (hipStream_t)stream>>>(q, k, v, out, H, T, (size_t)ldb, scale, frames);
-  return vcv_check_launch();
+  return frames ? attn_fwd_launch(q, k, v, out, B, H, dk, T, ldb, scale, frames, stream) : VCV_EINVAL;
 }
