@@ -72,8 +72,12 @@ typedef struct VcvConvArgs {
   const float* bias;  /* [G*Mg] or NULL */
   const float* res;   /* like y, or NULL */
   const float* mask;  /* [B, Tout] or NULL */
-  const float* xaux;  /* like x, for in_tf == DLEAKY/DRELU, else NULL */
-  const float* oaux;  /* like y, for out_tf != NONE, else NULL */
+  const float* xaux;  /* like x, for in_tf >= DLEAKY (the four derivative masks), else NULL */
+  const float* oaux;  /* like y, for out_tf != NONE, else NULL.  out_tf is one of VCV_TF_NONE, VCV_TF_DLEAKY, VCV_TF_DRELU,
+                         VCV_TF_DTANH: every entry point returns VCV_EINVAL, before any launch, for any other value
+                         (VCV_TF_LEAKY and VCV_TF_DLOGCLAMP included) and for out_tf != NONE with oaux == NULL.  in_tf is one
+                         of the six VCV_TF_* values for vcv_conv_gemm (VCV_EINVAL outside 0..5) and NONE / LEAKY for the
+                         packed-weight families */
   float* y;           /* [B, G*Mg, Tout, P] */
   int32_t B, G, Cg, Mg;
   int32_t Tin, Tout, P;

@@ -408,7 +408,11 @@ extern "C" int vcv_conv_gemm(const VcvConvArgs* args, void* stream) {
   if (a.B <= 0 || a.G <= 0 || a.Cg <= 0 || a.Mg <= 0 || a.Tin <= 0 || a.Tout <= 0 || a.P <= 0 ||
       a.K <= 0 || a.Q <= 0 || a.s <= 0)
     return VCV_EINVAL;
+  if (a.in_tf < VCV_TF_NONE || a.in_tf > VCV_TF_DLOGCLAMP) return VCV_EINVAL;
   if (a.in_tf >= VCV_TF_DLEAKY && !a.xaux) return VCV_EINVAL;
+  // the epilogue acts on these three derivative masks only (any other selector would be skipped, not applied)
+  if (a.out_tf != VCV_TF_NONE && a.out_tf != VCV_TF_DLEAKY && a.out_tf != VCV_TF_DRELU && a.out_tf != VCV_TF_DTANH)
+    return VCV_EINVAL;
   if (a.out_tf != VCV_TF_NONE && !a.oaux) return VCV_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const int U = a.Q * a.P;

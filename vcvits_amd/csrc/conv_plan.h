@@ -11,11 +11,16 @@ namespace {
 
 // One-group launches of the forward type (a_mode 0) or phased (transposed conv / strided data gradient, one residue per
 // phase), input transform none or a leaky-ReLU with slope in [0, 1), at least 32 rows x 16 reduction channels, at most 16
-// taps, tensors whose flattened rows index in 31 bits.  What the families differ in: s_le_3 (the family stages no span longer
+// taps, tensors whose flattened rows index in 31 bits, out_tf none or one of DLEAKY / DRELU / DTANH with `oaux` given.  What
+// the families differ in: s_le_3 (the family stages no span longer
 // than stride 3's); io (the storage combination of the instance: VcvConvArgs.io must match it, and only io != 0 has the
 // post-scale and the merged form, ms > 1: all output phases of a transposed conv as rows of one launch).
 inline bool conv_eligible(const VcvConvArgs& a, bool s_le_3, int io = 0) {
   if (a.io != io || (io == 0 && a.post_scale != 0.f)) return false;
+  // the epilogues act on these three derivative masks only, and read `oaux` for each of them
+  const bool out_tf_ok = a.out_tf == VCV_TF_NONE ||
+                         ((a.out_tf == VCV_TF_DLEAKY || a.out_tf == VCV_TF_DRELU || a.out_tf == VCV_TF_DTANH) && a.oaux);
+  if (!out_tf_ok) return false;
   const bool fwd_type = a.a_mode == 0 && a.phases <= 1;
   const bool phased = a.a_mode == 1 && a.phases > 1 && a.s == 1 && a.dj == -1;
   // (16-bit activations only: the epilogue that interleaves the phases)
@@ -67,9 +72,10 @@ inline double conv_round_fill_rows(const VcvConvArgs& a, int bm, int bn) {
 }
 
 // 16-byte epilogue through LDS (BfGeom.vec): output rows contiguous in the column index, room for a 32 x 40 float tile per
-// MFMA wave
+// MFMA wave.  It bounds a column by u < Q * P alone, so every q must be an output row (Q <= Tout): with more positions than
+// rows the scalar epilogue, which tests the row, takes the launch
 inline int conv_vec(const VcvConvArgs& a, int mfma_waves, size_t lds_bytes) {
-  return vcv_tuning().pk_vec && conv_phases(a) == 1 && a.os == 1 && a.oo == 0 && (!a.mask || a.P == 1) &&
+  return vcv_tuning().pk_vec && conv_phases(a) == 1 && a.os == 1 && a.oo == 0 && a.Q <= a.Tout && (!a.mask || a.P == 1) &&
          (size_t)mfma_waves * 32 * 40 * 4 <= lds_bytes;
 }
 
