@@ -543,6 +543,26 @@ int vcv_rel_attn_bwd2(const float* q, const float* k, const float* v, const floa
 int vcv_rel_attn_stream_supported(int B, int H, int dk, int T, int w);
 int vcv_rel_attn_stream_fwd(const float* q, const float* k, const float* v, const float* embk, const float* embv,
                             const float* mask, float* out, int B, int H, int dk, int T, int w, float qscale, void* stream);
+/* TRAINING through the streamed attention (attention_stream_grad.hip; relative_attention_transformer.py:150-182 and its
+ * autograd), same shapes and layouts, memory linear in T in both directions.
+ * vcv_rel_attn_stream_train_fwd: the streamed forward with dropout (`pdrop` in [0, 1), the mask of vcv_rel_attn_fwd for the
+ * same `seed`: a pure function of (seed, flat index in [B*H, T, T])) that also writes stats [B*H, T, 2] = (running max m_i,
+ * sum l_i of exp(s - m_i) before dropout) per query.
+ * vcv_rel_attn_stream_bwd (relative_attention_transformer.py:150-182, autograd): given the forward's `out` and `stats` and
+ * the upstream gradient dO, recomputes the probabilities tile by tile in two passes (queries: dq and the table gradients;
+ * keys: dk, dv) with one writer per output element: no atomics, so all five gradients are bit-reproducible.  `ws` holds
+ * vcv_rel_attn_stream_bwd_workspace() floats (delta, the band dot products and the per-block partial tables; linear in
+ * T; < 0 for a shape vcv_rel_attn_stream_supported refuses).
+ * Both entry points return VCV_EINVAL before any launch for a null pointer, an unsupported shape or pdrop outside [0, 1);
+ * under graph capture both add the same seed offset as the fused launchers. */
+int vcv_rel_attn_stream_train_fwd(const float* q, const float* k, const float* v, const float* embk, const float* embv,
+                                  const float* mask, float* out, float* stats, int B, int H, int dk, int T, int w, float qscale,
+                                  float pdrop, uint64_t seed, void* stream);
+long long vcv_rel_attn_stream_bwd_workspace(int B, int H, int dk, int T, int w);
+int vcv_rel_attn_stream_bwd(const float* q, const float* k, const float* v, const float* embk, const float* embv,
+                            const float* mask, const float* out, const float* stats, const float* dO, float* ws, float* dq,
+                            float* dk_out, float* dv, float* dembk, float* dembv, int B, int H, int dk, int T, int w, float qscale,
+                            float pdrop, uint64_t seed, void* stream);
 /* nn.Dropout (relative_attention_transformer.py:40,44,292): y = x * mask(seed, index) / (1-p); the
  * backward is the same call on dy with the same seed */
 int vcv_dropout(const float* x, float* y, int64_t n, float p, uint64_t seed, void* stream);

@@ -3,7 +3,12 @@ python tools/attn_bench.py [--dtype bf16] [--unfused] [--reps 20]
 
 python tools/attn_bench.py --stream [--out profiles/attn_stream_bench.txt]: the no-grad forward without `attn`, the streamed
 kernel (attention_stream.hip) against the path that runs today at the same shape (VCVITS_ATTN_STREAM_MIN_T = 0), alternating
-in one process, three runs each, device events; median (min ... max), TFLOP/s as 4 B H T^2 dk / t, peak allocated bytes."""
+in one process, three runs each, device events; median (min ... max), TFLOP/s as 4 B H T^2 dk / t, peak allocated bytes.
+
+python tools/attn_bench.py --stream-grad [--out profiles/attn_stream_grad_bench.txt]: forward + backward with want_attn=False at
+p = 0 and p = 0.1, the streamed training kernels (attention_stream_grad.hip, VCVITS_ATTN_STREAM_GRAD_MIN_T = 1) against the path
+that runs today (= 0) wherever that one can allocate, alternating, median of 3 from device events, peak allocated bytes, TFLOP/s
+as (4 + 14) B H T^2 dk / t."""
 import argparse
 import os
 import sys
@@ -19,6 +24,7 @@ ap.add_argument("--dtype", default="f32")
 ap.add_argument("--unfused", action="store_true")
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--stream", action="store_true")
+ap.add_argument("--stream-grad", action="store_true")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 ops.set_compute_dtype(a.dtype)
@@ -90,8 +96,82 @@ def stream_leg():
             f.write("\n".join(lines) + "\n")
 
 
+def stream_grad_leg():
+    lines = ["# tools/attn_bench.py --stream-grad --dtype %s: ops.rel_attention forward + backward, want_attn=False, ones mask, window 4." % a.dtype,
+             "# today = VCVITS_ATTN_STREAM_GRAD_MIN_T=0 (fused kernels at T <= 896, the three-launch path past it); streamed = 1.",
+             "# us per forward + backward: median (min ... max) of 3 runs, alternating, device events; TFLOP/s = 18 B H T^2 dk / median",
+             "# (4 forward + 14 backward, the streamed count, for both legs); of peak: against %.1f TFLOP/s of fp32 MFMA;" % PEAK_F32_MFMA,
+             "# peak MB: allocated over one forward + backward, inputs and dO not counted."]
+    shapes = [(16, 4, dk, T) for dk in (64, 32) for T in (500, 1000, 2000)] + [(1, 4, dk, T) for T in (4000, 15000) for dk in (64, 32)]
+    old = ops._ATTN_STREAM_GRAD_MIN_T[0]
+    try:
+        for B, H, dk, T in shapes:
+            t = lambda *s: torch.randn(*s, device=dev)
+            q, k, v = (2.0 * t(B, H * dk, T)).requires_grad_(True), t(B, H * dk, T).requires_grad_(True), t(B, H * dk, T).requires_grad_(True)
+            ek, ev = (t(1, 9, dk) * dk ** -0.5).requires_grad_(True), (t(1, 9, dk) * dk ** -0.5).requires_grad_(True)
+            gy = t(B, H * dk, T)
+            mask = torch.ones(B, T, device=dev)
+            flops = 18.0 * B * H * T * T * dk
+            reps = max(2, min(50, int(2e12 / flops)))
+            for p in (0.0, 0.1):
+                def call(min_t):
+                    ops._ATTN_STREAM_GRAD_MIN_T[0] = min_t
+                    for x in (q, k, v, ek, ev):
+                        x.grad = None
+                    o, _ = ops.rel_attention(q, k, v, ek, ev, mask, H, 4, p, training=p > 0, want_attn=False)
+                    o.backward(gy)
+
+                legs, times, peaks, why = [("streamed", 1)], {}, {}, None
+                if B * H * T * T >= 2 ** 31:
+                    why = "B H T^2 = %.2e elements is past the int indexing of the three-launch path" % (B * H * T * T)
+                else:
+                    legs.append(("today", 0))
+                for name, mt in list(legs):  # warm-up and the peak memory of one forward + backward
+                    try:
+                        call(mt)
+                        torch.cuda.synchronize()
+                        torch.cuda.reset_peak_memory_stats()
+                        base = torch.cuda.memory_allocated()
+                        call(mt)
+                        torch.cuda.synchronize()
+                        peaks[name] = torch.cuda.max_memory_allocated() - base
+                        times[name] = []
+                    except torch.cuda.OutOfMemoryError as e:
+                        legs.remove((name, mt))
+                        why = "out of memory (%s)" % str(e).split(".")[0]
+                        torch.cuda.empty_cache()
+                for _ in range(3):
+                    for name, mt in legs:
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        for _ in range(reps):
+                            call(mt)
+                        e1.record()
+                        torch.cuda.synchronize()
+                        times[name].append(e0.elapsed_time(e1) * 1e3 / reps)
+                n0 = len(lines)
+                for name, _ in legs:
+                    ts = sorted(times[name])
+                    lines.append("B=%-2d H=%d dk=%-2d T=%-5d p=%-3g %-8s %10.1f us (%9.1f ... %9.1f) %6.2f TFLOP/s %5.3f of peak  peak %9.1f MB  reps %d" % (
+                        B, H, dk, T, p, name, ts[1], ts[0], ts[2], flops / ts[1] / 1e6, flops / ts[1] / 1e6 / PEAK_F32_MFMA, peaks[name] / 1e6, reps))
+                if "today" in times and "streamed" in times:
+                    lines.append("    streamed / today = %.3f of the time, %.4f of the memory" % (
+                        sorted(times["streamed"])[1] / sorted(times["today"])[1], peaks["streamed"] / max(peaks["today"], 1)))
+                else:
+                    lines.append("    today: not run (%s)" % why)
+                print("\n".join(lines[n0:]), flush=True)
+    finally:
+        ops._ATTN_STREAM_GRAD_MIN_T[0] = old
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 if a.stream:
     stream_leg()
+    sys.exit(0)
+if a.stream_grad:
+    stream_grad_leg()
     sys.exit(0)
 for name, B, H, dk, T in (("base B16", 16, 4, 64, 204), ("base B32", 32, 4, 64, 204), ("48k B16", 16, 4, 32, 204), ("infer 48k", 64, 4, 32, 500)):
     t = lambda *s: torch.randn(*s, device=dev)

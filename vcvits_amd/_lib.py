@@ -84,7 +84,8 @@ def lib():
         for name in EXPORTS:
             fn = getattr(L, name)
             if name != "vcv_version":
-                fn.restype = (ctypes.c_int64 if name in ("vcv_conv_dma_workspace", "vcv_wgrad_bf16_scratch", "vcv_wgrad_x3_scratch", "vcv_layernorm_c_bwd_scratch", "vcv_resblock_pair_supported")
+                fn.restype = (ctypes.c_int64 if name in ("vcv_conv_dma_workspace", "vcv_wgrad_bf16_scratch", "vcv_wgrad_x3_scratch", "vcv_layernorm_c_bwd_scratch", "vcv_resblock_pair_supported",
+                                                                "vcv_rel_attn_stream_bwd_workspace")
                               else ctypes.c_void_p if name == "vcv_get_seed_offset_ptr" else ctypes.c_int)
                 fn.argtypes = _ARGTYPES[name]
         _lib = L
@@ -112,6 +113,7 @@ EXPORTS = [
     "vcv_hubert_bias_gelu", "vcv_hubert_groupnorm_gelu", "vcv_hubert_layernorm_c_gelu", "vcv_hubert_attn_supported", "vcv_hubert_attn_fwd",
     "vcv_hubert_groupnorm_gelu_len", "vcv_hubert_mask_frames", "vcv_hubert_attn_fwd_len",
     "vcv_rel_attn_stream_supported", "vcv_rel_attn_stream_fwd",
+    "vcv_rel_attn_stream_train_fwd", "vcv_rel_attn_stream_bwd_workspace", "vcv_rel_attn_stream_bwd",
 ]
 
 
@@ -260,6 +262,9 @@ _ARGTYPES = {
     "vcv_hubert_attn_fwd_len": [_P, _P, _P, _P, _I, _I, _I, _I, _L, _F, _P, _P],
     "vcv_rel_attn_stream_supported": [_I, _I, _I, _I, _I],
     "vcv_rel_attn_stream_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
+    "vcv_rel_attn_stream_train_fwd": [_P] * 8 + [_I] * 5 + [_F, _F, ctypes.c_uint64, _P],
+    "vcv_rel_attn_stream_bwd_workspace": [_I, _I, _I, _I, _I],
+    "vcv_rel_attn_stream_bwd": [_P] * 15 + [_I] * 5 + [_F, _F, ctypes.c_uint64, _P],
 }
 
 

@@ -152,6 +152,50 @@ def _rel_attn_stream(q, k, v, embk, embv, mask, n_heads, window):
     return out
 
 
+class _RelAttnStreamFn(torch.autograd.Function):
+    """Training through the streamed kernels (attention_stream_grad.hip): one launch forward that keeps two floats per query
+    (running max, sum), and a backward pass that recomputes the probabilities from them in two passes.  Nothing of size
+    T x T is allocated in either direction; the dropout mask is regenerated from the seed."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, embk, embv, mask, n_heads, window, pdrop, seed):
+        q, k, v, embk, embv, mask = (_f32c(t) for t in (q, k, v, embk, embv, mask))
+        B, C, T = q.shape
+        H = n_heads
+        dk = C // H
+        qscale = 1.0 / (dk ** 0.5)
+        out = torch.empty_like(q)
+        stats = torch.empty((B * H, T, 2), device=q.device, dtype=torch.float32)
+        check(lib().vcv_rel_attn_stream_train_fwd(ptr(q), ptr(k), ptr(v), ptr(embk), ptr(embv), ptr(mask), ptr(out), ptr(stats),
+                                                  B, H, dk, T, window, qscale, pdrop, seed, stream()), "vcv_rel_attn_stream_train_fwd")
+        LAUNCH_COUNTS["attn_stream_grad"] += 1
+        ctx.cfg = (H, window, qscale, pdrop, seed)
+        ctx.save_for_backward(q, k, v, embk, embv, mask, out, stats)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        q, k, v, embk, embv, mask, out, stats = ctx.saved_tensors
+        H, window, qscale, pdrop, seed = ctx.cfg
+        dout = _f32c(dout)
+        B, C, T = q.shape
+        dk = C // H
+        ws = torch.empty((lib().vcv_rel_attn_stream_bwd_workspace(B, H, dk, T, window),), device=q.device, dtype=torch.float32)
+        dq, dkk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        dembk, dembv = torch.empty_like(embk), torch.empty_like(embv)
+        check(lib().vcv_rel_attn_stream_bwd(ptr(q), ptr(k), ptr(v), ptr(embk), ptr(embv), ptr(mask), ptr(out), ptr(stats), ptr(dout),
+                                            ptr(ws), ptr(dq), ptr(dkk), ptr(dv), ptr(dembk), ptr(dembv), B, H, dk, T, window, qscale,
+                                            pdrop, seed, stream()), "vcv_rel_attn_stream_bwd")
+        return dq, dkk, dv, dembk, dembv, None, None, None, None, None
+
+
+# the streamed TRAINING path (attention_stream_grad.hip) takes the calls with gradients and without `attn` from this T on,
+# dropout included; 0 (the default): never, every call keeps the path it had
+_ATTN_STREAM_GRAD_MIN_T = [tuning.integer("VCVITS_ATTN_STREAM_GRAD_MIN_T", 0, "shortest T at which relative-position attention "
+                                          "with gradients runs on the streamed kernels (memory linear in T; 0: never)")]
+
+
 def rel_attention(q, k, v, emb_rel_k, emb_rel_v, mask, n_heads, window, pdrop=0.0, training=False, want_attn=True):
     """Self-attention with shared-head windowed relative embeddings; mask [B,T] (key/query
     validity).  Returns (out [B,C,T], attn [B,H,T,T] -- None when want_attn is False on the fused path)."""
@@ -160,8 +204,12 @@ def rel_attention(q, k, v, emb_rel_k, emb_rel_v, mask, n_heads, window, pdrop=0.
     B, C, T = q.shape
     if p > 0 and DROPOUT_TRACE[0] is not None:
         DROPOUT_TRACE[0].append(("attn", p, seed, (B * n_heads, T, T)))
+    needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v, emb_rel_k, emb_rel_v))
+    if (needs_grad and not want_attn and 0 < _ATTN_STREAM_GRAD_MIN_T[0] <= T and
+            lib().vcv_rel_attn_stream_supported(B, n_heads, C // n_heads, T, window) == 0):
+        return _RelAttnStreamFn.apply(q, k, v, emb_rel_k, emb_rel_v, mask, n_heads, window, p, seed), None
     if (p == 0 and not want_attn and 0 < _ATTN_STREAM_MIN_T[0] <= T and
-            not (torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v, emb_rel_k, emb_rel_v))) and
+            not needs_grad and
             lib().vcv_rel_attn_stream_supported(B, n_heads, C // n_heads, T, window) == 0):
         return _rel_attn_stream(q, k, v, emb_rel_k, emb_rel_v, mask, n_heads, window), None
     if _ATTN_FUSED[0] and lib().vcv_rel_attn_supported(B, n_heads, C // n_heads, T, window) == 0:
