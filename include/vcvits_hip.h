@@ -270,12 +270,17 @@ int vcv_wgrad_bf16_set_force(int cand, int z);
  * 1024->1, discriminator.py:25,61; generator conv_post 32->1 + tanh) and the weight gradient of a
  * conv with one output or one input channel (conv_post / first layers, discriminator.py:18,53).
  * x [B,C,Tin,P], w [1,C,K], y [B,1,Tout,P]; in_leaky / out_act as in vcv_conv_gemm.
+ * vcv_conv_m1_fwd takes the Tout it is given (rows past the input read zeros) and any K at stride 1 with
+ * (K-1)*dil*P <= 256 (the LDS-staged kernel); every other launch (a stride, a wider halo) has K <= 16, VCV_EINVAL past it.
  * vcv_thin_wgrad: dw[m,c,k] += alpha * sum tf(a[b,m,q,p]) * tf(bsh[b,c,q*s+k*d+off,p]), K <= 16. */
 int vcv_conv_m1_fwd(const float* x, const float* w, const float* bias, float* y, int B, int C, int Tin,
                     int Tout, int P, int K, int stride, int dil, int pad, int in_leaky, int out_act,
                     float slope, void* stream);
-/* One INPUT channel (first discriminator layers, discriminator.py:18,53): x [B,1,Tin,P], w [M,1,K] (M <= 64,
- * K <= 16), y / dy [B,M,Tout,P].  Forward fuses bias + out_act; dgrad gives dx [B,1,Tin,P] (overwrites). */
+/* One INPUT channel (first discriminator layers, discriminator.py:18,53): x [B,1,Tin,P], w [M,1,K] (K <= 16),
+ * y / dy [B,M,Tout,P].  Forward fuses bias + out_act and takes ANY M: the launcher runs it in chunks of <= 64 output
+ * channels (the heads' data gradient below runs it at M = 1024).  vcv_conv_c1_dgrad alone has the limit M <= 64 (its
+ * weights sit in one LDS block) and returns VCV_EINVAL past it; it gives dx [B,1,Tin,P] (overwrites; rows of x that no
+ * tap reaches are written as 0).  K > 16 is VCV_EINVAL for all four. */
 int vcv_conv_c1_fwd(const float* x, const float* w, const float* bias, float* y, int B, int M, int Tin, int Tout,
                     int P, int K, int stride, int dil, int pad, int out_act, float slope, void* stream);
 /* The same with y[b,m,t,p] *= leaky'(oaux[b,m,t,p]) in the epilogue (oaux may be NULL): the data gradient of a one-OUTPUT-
@@ -292,8 +297,9 @@ int vcv_conv_c1_fwd_flip(const float* x, const float* w, const float* bias, floa
 int vcv_conv_c1_dgrad(const float* dy, const float* w, float* dx, int B, int M, int Tin, int Tout, int P, int K,
                       int stride, int dil, int pad, void* stream);
 /* One-frame pointwise layers (speaker conditioning `cond_layer` / `cond`: Conv1d(gin, M, 1) applied to g [B, gin, 1],
- * modules.py:126-131 and the hub generator): x [B, C], w [M, C], y / dy [B, M], B <= 32.  Forward fuses the bias;
- * dgrad overwrites dx [B, C]; wgrad ADDS onto dw [M, C]. */
+ * modules.py:126-131 and the hub generator): x [B, C], w [M, C], y / dy [B, M].  Forward fuses the bias; dgrad
+ * overwrites dx [B, C]; both hold one accumulator per batch element in registers: B <= 32, VCV_EINVAL past it.  wgrad
+ * ADDS onto dw [M, C] and loops over any B. */
 int vcv_linear_t1_fwd(const float* x, const float* w, const float* bias, float* y, int B, int C, int M, void* stream);
 int vcv_linear_t1_dgrad(const float* dy, const float* w, float* dx, int B, int C, int M, void* stream);
 int vcv_linear_t1_wgrad(const float* dy, const float* x, float* dw, int B, int C, int M, void* stream);

@@ -167,6 +167,28 @@ def conv(g, x, w, y_prior, *, flip=0, bias=None, res=None, mask=None, xaux=None,
     return y.reshape(B, G * Mg, g.Tout, P), S.reshape(B, G * Mg, g.Tout, P)
 
 
+def dgrad(dy, w, Tin, s, dil, pad, dtype=torch.float64):
+    """The data gradient of a conv with ANY stride and dilation together, which no single VcvConvArgs launch expresses (the
+    a_mode-1 form wants stride 1, the phased form dilation 1): dy [B, M, Tout, P], w [M, C, K] ->
+        dx[b, c, t, p] = sum_{m, k, q: q*s + k*dil - pad == t} w[m, c, k] * dy[b, m, q, p]     (dx [B, C, Tin, P] in `dtype`),
+    and S, the float64 sum of magnitudes behind every element (0 on a row no tap reaches).  By explicit scatter."""
+    dy_ = dy.detach().cpu().to(dtype)
+    w_ = w.detach().cpu().to(dtype)
+    B, M, Tout, P = dy_.shape
+    Cin, K = w_.shape[1], w_.shape[2]
+    dx = torch.zeros(B, Cin, Tin, P, dtype=dtype)
+    S = torch.zeros(B, Cin, Tin, P, dtype=torch.float64)
+    q = torch.arange(Tout)
+    for k in range(K):
+        t = q * s + k * dil - pad
+        ok = (t >= 0) & (t < Tin)
+        if not bool(ok.any()):
+            continue
+        dx[:, :, t[ok], :] += torch.einsum("mc,bmqp->bcqp", w_[:, :, k], dy_[:, :, q[ok], :])
+        S[:, :, t[ok], :] += torch.einsum("mc,bmqp->bcqp", w_[:, :, k].double().abs(), dy_[:, :, q[ok], :].double().abs())
+    return dx, S
+
+
 def gamma(n):
     """gamma_n = n u / (1 - n u), u = 2^-24: the relative bound on an fp32 sum of n terms in any order (Higham, Accuracy and
     Stability of Numerical Algorithms, section 3.1)."""

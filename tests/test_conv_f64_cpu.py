@@ -185,3 +185,71 @@ def test_rounded_operands_and_gamma():
     got = C.conv(g, x, w, prior, in_tf=C.TF_LEAKY, slope=0.1, rounded=True)[0]
     assert torch.equal(got, _fconv(rb(xl), rb(w), 1, 1, 1))
     assert C.gamma(100) == pytest.approx(100 * 2.0 ** -24, rel=1e-4) and C.gamma(1) > 2.0 ** -24
+
+
+THIN_DGRAD = [(2, 1, 5, 40, 1, 5, 3, 2, 2), (2, 1, 33, 23, 3, 15, 2, 7, 2), (1, 1, 16, 50, 1, 16, 3, 0, 1), (2, 3, 4, 31, 2, 4, 2, 3, 3),
+              (2, 1, 7, 29, 1, 1, 3, 0, 2), (2, 1, 6, 30, 1, 5, 1, 2, 2)]
+
+
+@pytest.mark.parametrize("shape", THIN_DGRAD, ids=lambda s: "B%d-C%d-M%d-T%d-P%d-K%d-s%d-pad%d-dil%d" % s)
+def test_strided_dilated_data_gradient_is_autograd(shape):
+    """conv_f64.dgrad (stride and dilation together: vcv_conv_c1_dgrad takes both) is the float64 autograd data gradient, its S
+    the same gradient of the magnitudes; rows of x past the last one a tap reaches come back as exact zeros with S = 0; and
+    where one VcvConvArgs launch expresses the gradient (stride 1, or dilation 1) conv() gives the same numbers."""
+    B, Cin, M, T, P, K, s, pad, dil = shape
+    rng = _rng(shape)
+    Tout = _out_len(T, K, s, pad, dil)
+    last = (Tout - 1) * s + (K - 1) * dil - pad  # the last row of x a tap reaches
+    T = max(T, last + 1) + 4  # (four rows no output touches)
+    x0 = _t(rng, B, Cin, T, P).requires_grad_()
+    w = _t(rng, M, Cin, K)
+    dy = _t(rng, B, M, Tout, P)
+    y = _fconv(x0, w, s, pad, dil)[:, :, :Tout]
+    ref = torch.autograd.grad(y, x0, dy)[0]
+    got, S = C.dgrad(dy, w, T, s, dil, pad)
+    assert C.dist(got, ref) <= TOL
+    xa = x0.detach().clone().requires_grad_()
+    Sref = torch.autograd.grad(_fconv(xa, w.abs(), s, pad, dil)[:, :, :Tout], xa, dy.abs())[0]
+    assert C.dist(S, Sref) <= TOL
+    assert last < T - 1 and not bool(got[:, :, last + 1:].any()) and not bool(S[:, :, last + 1:].any())
+    prior = torch.zeros(B, Cin, T, P, dtype=torch.float64)
+    if s == 1:
+        g = C.geom(B, 1, M, Cin, Tout, T, P, K, 1, -dil, pad, Q=T, a_mode=1)
+        assert C.dist(C.conv(g, dy, w, prior)[0], got) <= TOL
+    elif dil == 1:
+        g = C.geom(B, 1, M, Cin, Tout, T, P, K, 1, -1, 0, s, -pad, s, (T - 1 + pad) // s + 1, 1)
+        assert C.dist(C.conv(g, dy, w, prior)[0], got) <= TOL
+
+
+@pytest.mark.parametrize("K", [4, 5])
+def test_single_channel_taps_reversed_and_masked(K):
+    """The forms vcv_conv_c1_fwd_flip runs: Cg = 1 with flip = 1 is the convolution with every weight row read backwards
+    (A(m, 0, k) = w[m, K-1-k]; [1, M, K] and [M, 1, K] are the same memory), and with pad' = (K-1)*dil - pad that is the
+    autograd data gradient of a one-OUTPUT-channel conv; out_tf DLEAKY on top is the derivative of the leaky-ReLU in front."""
+    rng = _rng(("c1flip", K))
+    B, M, T, P, dil, pad = 2, 6, 21, 2, 2, 3
+    w = _t(rng, 1, M, K)  # the forward conv's weight [1, C = M, K]
+    x0 = _t(rng, B, M, T, P).requires_grad_()
+    Tout = _out_len(T, K, 1, pad, dil)
+    dy = _t(rng, B, 1, Tout, P)
+    prior = torch.zeros(B, M, T, P, dtype=torch.float64)
+    g = C.geom(B, 1, 1, M, Tout, T, P, K, 1, dil, pad - (K - 1) * dil)
+    got = C.conv(g, dy, w, prior, flip=1)[0]
+    assert C.dist(got, torch.autograd.grad(_fconv(x0, w, 1, pad, dil), x0, dy)[0]) <= TOL
+    assert C.dist(got, _fconv(dy, w.flip(2).reshape(M, 1, K), 1, (K - 1) * dil - pad, dil)) <= TOL
+    sl = C.f32(0.1)
+    ref = torch.autograd.grad(_fconv(F.leaky_relu(x0, sl), w, 1, pad, dil), x0, dy)[0]
+    assert C.dist(C.conv(g, dy, w, prior, flip=1, out_tf=C.TF_DLEAKY, oaux=x0.detach(), slope=0.1)[0], ref) <= TOL
+
+
+def test_one_output_channel_with_more_or_fewer_rows_than_the_formula():
+    """vcv_conv_m1_fwd is handed Tout: fewer rows than Tin + 2*pad - dil*(K-1) are the first rows of the convolution, more read
+    zeros past the input (the bias and the activation still apply)."""
+    rng = _rng("m1rows")
+    B, Cin, T, P, K, pad = 2, 17, 30, 2, 3, 1
+    x, w, bias = _t(rng, B, Cin, T, P), _t(rng, 1, Cin, K), _t(rng, 1)
+    full = torch.tanh(_fconv(F.pad(F.leaky_relu(x, C.f32(0.1)), (0, 0, 0, 2)), w, 1, pad, 1) + bias.view(1, 1, 1, 1))
+    for Tout in (T - 3, T + 2):
+        g = C.geom(B, 1, Cin, 1, T, Tout, P, K, 1, 1, -pad)
+        y, _ = C.conv(g, x, w, torch.zeros(B, 1, Tout, P, dtype=torch.float64), bias=bias, in_tf=C.TF_LEAKY, out_act=C.ACT_TANH, slope=0.1)
+        assert C.dist(y, full[:, :, :Tout]) <= TOL

@@ -4,6 +4,9 @@ csrc/wgrad_bf16.hip.
 1. The formula of include/vcvits_hip.h (VcvWgradArgs, G = 1), by explicit index gather -- no torch.nn.functional.conv*:
      dw[m, c, k] = sum_{b, q, p} tfa(a[b, m, q, p]) * tfb(x[b, c, q * s + k * dj + off, p]),  rows outside [0, Tb) read zero
    in the dtype it is asked for, so the same text is the float64 yardstick and the float32 reference computation.
+   The derivative transforms of vcv_thin_wgrad (DLEAKY / DRELU / DTANH / DLOGCLAMP, each a function of an aux tensor of the
+   operand's shape) are restated here too; the MFMA kernels refuse them.  wgrad_mag() is the sum of magnitudes behind every
+   element, which scales the element-wise rounding bound of tests/test_conv_thin_abi_gpu.py.
    rounded=True rounds every operand to bf16 AFTER its leaky-ReLU (which the kernel forms in float32: fmaxf(f, f * slope)),
    as the bf16 entry point does, before the sum.  dbias(a) is the row sum of the UNROUNDED `a`: the kernel takes it from its
    fp32 staging registers in both arithmetics.
@@ -13,10 +16,11 @@ csrc/wgrad_bf16.hip.
 
 Shares no code with vcvits_amd."""
 import collections
+import math
 
 import torch
 
-TF_NONE, TF_LEAKY, TF_DLEAKY = 0, 1, 2  # include/vcvits_hip.h
+TF_NONE, TF_LEAKY, TF_DLEAKY, TF_DRELU, TF_DTANH, TF_DLOGCLAMP = 0, 1, 2, 3, 4, 5  # include/vcvits_hip.h
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -27,10 +31,12 @@ def bf16_round(t):
     return t.float().bfloat16().float()
 
 
-def operand(t, tf, slope, rounded, dtype):
-    """tf(t) as the kernel's MFMA sees it.  rounded: leaky-ReLU in float32 as the kernel forms it, then bf16."""
+def operand(t, tf, slope, rounded, dtype, aux=None):
+    """tf(t) as the kernel sees it.  rounded: leaky-ReLU in float32 as the kernel forms it, then bf16.  aux: the tensor the
+    derivative transforms are a function of (the activation's output; for the leaky-ReLU its input has the same sign)."""
     t = t.detach().cpu()
     if rounded:
+        assert tf in (TF_NONE, TF_LEAKY)
         t = t.float()
         if tf == TF_LEAKY:
             t = torch.maximum(t, t * torch.tensor(slope, dtype=torch.float32))
@@ -39,15 +45,32 @@ def operand(t, tf, slope, rounded, dtype):
     if tf == TF_LEAKY:
         # the float32 NUMBER the library is handed as slope (the exact pass uses 0.5; 0.1 is not a float32)
         t = torch.maximum(t, t * float(torch.tensor(slope, dtype=torch.float32)))
+    elif tf != TF_NONE:
+        sl = float(torch.tensor(slope, dtype=torch.float32))
+        x = aux.detach().cpu().to(dtype)
+        assert x.shape == t.shape
+        if tf == TF_DLEAKY:
+            t = t * torch.where(x > 0, torch.ones_like(x), torch.full_like(x, sl))
+        elif tf == TF_DRELU:
+            t = torch.where(x > 0, t, torch.zeros_like(t))
+        elif tf == TF_DTANH:
+            t = t * (1 - x * x)
+        elif tf == TF_DLOGCLAMP:
+            t = torch.where(x > math.log(sl), t * torch.exp(-x), torch.zeros_like(t))
+        else:
+            raise ValueError("transform %r" % (tf,))
     return t
 
 
-def wgrad(a, b, K, s, dj, off, a_tf=TF_NONE, b_tf=TF_NONE, slope=0.1, rounded=False, dtype=torch.float64):
-    """a [B, M, Ta, P], b [B, C, Tb, P] -> dw [M, C, K] in `dtype`."""
+def wgrad(a, b, K, s, dj, off, a_tf=TF_NONE, b_tf=TF_NONE, slope=0.1, rounded=False, dtype=torch.float64, aaux=None, baux=None,
+          magnitudes=False):
+    """a [B, M, Ta, P], b [B, C, Tb, P] -> dw [M, C, K] in `dtype`.  magnitudes: sum |tfa(a)| |tfb(b)| instead."""
     assert a.dim() == 4 and b.dim() == 4 and a.shape[0] == b.shape[0] and a.shape[3] == b.shape[3]
     Ta, Tb = a.shape[2], b.shape[2]
-    ta = operand(a, a_tf, slope, rounded, dtype)
-    tb = operand(b, b_tf, slope, rounded, dtype)
+    ta = operand(a, a_tf, slope, rounded, dtype, aaux)
+    tb = operand(b, b_tf, slope, rounded, dtype, baux)
+    if magnitudes:
+        ta, tb = ta.abs(), tb.abs()
     dw = torch.zeros(a.shape[1], b.shape[1], K, dtype=dtype)
     q = torch.arange(Ta)
     for k in range(K):
@@ -58,6 +81,11 @@ def wgrad(a, b, K, s, dj, off, a_tf=TF_NONE, b_tf=TF_NONE, slope=0.1, rounded=Fa
         xk = tb[:, :, rows.clamp(0, Tb - 1), :] * ok.to(dtype).view(1, 1, Ta, 1)  # [B, C, Ta, P]
         dw[:, :, k] = torch.einsum("bmqp,bcqp->mc", ta, xk)
     return dw
+
+
+def wgrad_mag(a, b, K, s, dj, off, **kw):
+    """S[m, c, k] = sum |tfa(a)| |tfb(b)| in float64"""
+    return wgrad(a, b, K, s, dj, off, magnitudes=True, dtype=torch.float64, **kw)
 
 
 def dbias(a, dtype=torch.float64):
