@@ -549,6 +549,12 @@ int vcv_rel_attn_bwd2(const float* q, const float* k, const float* v, const floa
 int vcv_rel_attn_stream_supported(int B, int H, int dk, int T, int w);
 int vcv_rel_attn_stream_fwd(const float* q, const float* k, const float* v, const float* embk, const float* embv,
                             const float* mask, float* out, int B, int H, int dk, int T, int w, float qscale, void* stream);
+/* vcv_rel_attn_stream_fwd (relative_attention_transformer.py:150-182) with bf16 OPERANDS: q, k and v are rounded to bf16
+ * (nearest even; q unscaled, qscale multiplies the fp32 score) and the probabilities are rounded to bf16 as the operand of
+ * the second product; both contractions on the bf16 matrix cores, accumulation, max, sum and the relative-position terms in
+ * fp32 on unrounded values.  Same arguments, same shapes (vcv_rel_attn_stream_supported), same refusals. */
+int vcv_rel_attn_stream_fwd_bf16(const float* q, const float* k, const float* v, const float* embk, const float* embv,
+                                 const float* mask, float* out, int B, int H, int dk, int T, int w, float qscale, void* stream);
 /* TRAINING through the streamed attention (attention_stream_grad.hip; relative_attention_transformer.py:150-182 and its
  * autograd), same shapes and layouts, memory linear in T in both directions.
  * vcv_rel_attn_stream_train_fwd: the streamed forward with dropout (`pdrop` in [0, 1), the mask of vcv_rel_attn_fwd for the
@@ -712,6 +718,14 @@ int vcv_hubert_attn_fwd(const float* q, const float* k, const float* v, float* o
  * t >= frames[b] are never used, whatever they hold; out[b, :, t] is exact 0 for t >= frames[b]. */
 int vcv_hubert_attn_fwd_len(const float* q, const float* k, const float* v, float* out, int B, int H, int dk, int T,
                             int64_t ldb, float scale, const int* frames, void* stream);
+/* vcv_hubert_attn_fwd and vcv_hubert_attn_fwd_len with bf16 OPERANDS: q, k and v are rounded to bf16 (nearest even; q
+ * unscaled, `scale` multiplies the fp32 score) and the probabilities are rounded to bf16 as the operand of the second
+ * product; both contractions on the bf16 matrix cores, accumulation, max and sum in fp32.  Same arguments, same shapes
+ * (vcv_hubert_attn_supported), same refusals and the same meaning of `frames`. */
+int vcv_hubert_attn_fwd_bf16(const float* q, const float* k, const float* v, float* out, int B, int H, int dk, int T,
+                             int64_t ldb, float scale, void* stream);
+int vcv_hubert_attn_fwd_len_bf16(const float* q, const float* k, const float* v, float* out, int B, int H, int dk, int T,
+                                 int64_t ldb, float scale, const int* frames, void* stream);
 
 /* returns a static string describing the build (arch, kernel variants) */
 const char* vcv_version(void);

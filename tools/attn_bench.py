@@ -5,6 +5,10 @@ python tools/attn_bench.py --stream [--out profiles/attn_stream_bench.txt]: the 
 kernel (attention_stream.hip) against the path that runs today at the same shape (VCVITS_ATTN_STREAM_MIN_T = 0), alternating
 in one process, three runs each, device events; median (min ... max), TFLOP/s as 4 B H T^2 dk / t, peak allocated bytes.
 
+python tools/attn_bench.py --stream --bf16 [--out profiles/attn_stream_bf16_bench.txt]: the streamed forward in bf16 compute mode
+with VCVITS_ATTN_STREAM_BF16 = 1 (attention_stream_bf16.hip, bf16 operands) against = 0 (the fp32-operand kernel, what bf16 mode
+runs by default), alternating in one process, five runs each, device events; with --out the lines are appended.
+
 python tools/attn_bench.py --stream-grad [--out profiles/attn_stream_grad_bench.txt]: forward + backward with want_attn=False at
 p = 0 and p = 0.1, the streamed training kernels (attention_stream_grad.hip, VCVITS_ATTN_STREAM_GRAD_MIN_T = 1) against the path
 that runs today (= 0) wherever that one can allocate, alternating, median of 3 from device events, peak allocated bytes, TFLOP/s
@@ -25,6 +29,7 @@ ap.add_argument("--unfused", action="store_true")
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--stream", action="store_true")
 ap.add_argument("--stream-grad", action="store_true")
+ap.add_argument("--bf16", action="store_true", help="with --stream: the bf16-operand streamed kernel against the fp32-operand one")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 ops.set_compute_dtype(a.dtype)
@@ -93,6 +98,62 @@ def stream_leg():
         ops._ATTN_STREAM_MIN_T[0] = old
     if a.out:
         with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+def stream_bf16_leg():
+    lines = ["# tools/attn_bench.py --stream --bf16: ops.rel_attention under no_grad, want_attn=False, ones mask, window 4, H = 4, bf16",
+             "# compute mode, VCVITS_ATTN_STREAM_MIN_T=1.  fp32 = VCVITS_ATTN_STREAM_BF16=0 (rel_attn_stream_fwd_kernel, fp32 operands, the",
+             "# default); bf16 = 1 (rel_attn_stream_fwd_bf16_kernel).  us per call: median (min ... max) of 5 runs after a warm-up call,",
+             "# alternating in one process, device events; TFLOP/s = 4 B H T^2 dk / median; rel_l2: ||bf16 - fp32|| / ||fp32|| of the outputs."]
+    shapes = [(B, 4, dk, T) for T in (1000, 4000, 15000) for B in (1, 8) for dk in (32, 64)]
+    old = ops._ATTN_STREAM_MIN_T[0], ops._ATTN_STREAM_BF16[0], ops.compute_dtype()
+    ops._ATTN_STREAM_MIN_T[0] = 1
+    ops.set_compute_dtype("bf16")
+    try:
+        for B, H, dk, T in shapes:
+            t = lambda *s: torch.randn(*s, device=dev)
+            q, k, v = 2.0 * t(B, H * dk, T), t(B, H * dk, T), t(B, H * dk, T)
+            ek, ev = t(1, 9, dk) * dk ** -0.5, t(1, 9, dk) * dk ** -0.5
+            mask = torch.ones(B, T, device=dev)
+            flops = 4.0 * B * H * T * T * dk
+            reps = max(2, min(10 * a.reps, int(4e12 / flops)))  # a timed window of tens of milliseconds at the least
+            legs = (("fp32", 0, "attn_stream"), ("bf16", 1, "attn_stream_bf16"))
+
+            def call(sw):
+                ops._ATTN_STREAM_BF16[0] = sw
+                with torch.no_grad():
+                    return ops.rel_attention(q, k, v, ek, ev, mask, H, 4, want_attn=False)[0]
+
+            outs, times = {}, {n: [] for n, _, _ in legs}
+            for name, sw, key in legs:  # warm-up, the outputs for the comparison, and that the leg ran the kernel it names
+                before = ops.LAUNCH_COUNTS[key]
+                outs[name] = call(sw)
+                torch.cuda.synchronize()
+                assert ops.LAUNCH_COUNTS[key] == before + 1, (name, key)
+            for _ in range(5):
+                for name, sw, _ in legs:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(reps):
+                        call(sw)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    times[name].append(e0.elapsed_time(e1) * 1e3 / reps)
+            n0 = len(lines)
+            for name, _, _ in legs:
+                ts = sorted(times[name])
+                lines.append("B=%-2d H=%d dk=%-2d T=%-5d %-5s %10.1f us (%9.1f ... %9.1f) %7.2f TFLOP/s  reps %d" % (
+                    B, H, dk, T, name, ts[2], ts[0], ts[4], flops / ts[2] / 1e6, reps))
+            lines.append("    bf16 / fp32 = %.3f of the time; rel_l2 = %.1e" % (
+                sorted(times["bf16"])[2] / sorted(times["fp32"])[2], float((outs["bf16"] - outs["fp32"]).norm() / outs["fp32"].norm())))
+            print("\n".join(lines[n0:]), flush=True)
+            del outs
+    finally:
+        ops._ATTN_STREAM_MIN_T[0], ops._ATTN_STREAM_BF16[0] = old[0], old[1]
+        ops.set_compute_dtype(old[2])
+    if a.out:
+        with open(a.out, "a") as f:
             f.write("\n".join(lines) + "\n")
 
 
@@ -168,7 +229,7 @@ def stream_grad_leg():
 
 
 if a.stream:
-    stream_leg()
+    stream_bf16_leg() if a.bf16 else stream_leg()
     sys.exit(0)
 if a.stream_grad:
     stream_grad_leg()

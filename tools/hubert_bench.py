@@ -21,6 +21,11 @@ lengths are spread evenly over 3 to 10 s), extract_features(lengths=) and prepro
   equal      ms per batch of 16 equal rows of 10 s with lengths= (all rows full) and without
 Every pair is measured as alternating runs in one process, three each; the median and the range (min, max) are reported.
 
+--attn-bf16 replaces them by one line: bf16 mode with VCVITS_ATTN_STREAM_BF16 = 0 (the fp32-operand attention kernel, the
+default) and = 1 (the bf16-operand kernel, attention_stream_bf16.hip) at one architecture (--arch, default base: 12 layers) and
+--batch x --seconds, alternating in one process, five runs of --steps calls each after --warmup calls: ms per batch, the attention
+class of a separate pass with an event pair around every launch wrapper, and the relative L2 distance of the two outputs.
+
 There is no CPU path: without a GPU this fails."""
 import argparse
 import json
@@ -162,6 +167,56 @@ def _alternate(fa, fb, runs=3):
     return _stats(a), _stats(b)
 
 
+def attn_bf16(arch, batch, seconds, steps, warmup):
+    torch.manual_seed(0)
+    model = HubertFeatureExtractor(**ARCHS[arch]).to("cuda")
+    T = int(seconds * 16000)
+    src = (0.1 * torch.randn(batch, T, generator=torch.Generator().manual_seed(1))).to("cuda")
+    old = ops._ATTN_STREAM_BF16[0]
+    ops.set_compute_dtype("bf16")
+
+    def per_batch(sw):
+        def run():
+            ops._ATTN_STREAM_BF16[0] = sw
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(steps):
+                model.extract_features(src)
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / steps
+        return run
+
+    try:
+        outs, attn_ms, launches = {}, {}, {}
+        for sw in (0, 1):
+            ops._ATTN_STREAM_BF16[0] = sw
+            for _ in range(warmup):
+                model.extract_features(src)
+            before = ops.LAUNCH_COUNTS["attn_stream_bf16"]
+            with Classes() as c:
+                outs[sw] = model.extract_features(src)[0]
+                attn_ms[sw] = c.totals()["attention"]
+            launches[sw] = ops.LAUNCH_COUNTS["attn_stream_bf16"] - before
+        off, on = _alternate(per_batch(0), per_batch(1), runs=5)
+    finally:
+        ops._ATTN_STREAM_BF16[0] = old
+        ops.set_compute_dtype("f32")
+    a = ARCHS[arch]
+    assert launches == {0: 0, 1: a["layers"]}, launches
+    d = a["embed_dim"] // a["heads"]
+    frames = model.out_frames(T)
+    attn_flops = 4.0 * batch * a["heads"] * frames * frames * d * a["layers"]
+    return {"tool": "hubert_bench", "leg": "attn_bf16", "arch": arch, "mode": "bf16", "layers": a["layers"], "batch": batch,
+            "seconds": seconds, "frames": frames, "head_dim": d,
+            "ms_per_batch": {"switch_0_fp32_operands": off, "switch_1_bf16_operands": on},
+            "attention_ms": {"switch_0_fp32_operands": round(attn_ms[0], 3), "switch_1_bf16_operands": round(attn_ms[1], 3)},
+            "attention_tflops": {"switch_0_fp32_operands": round(attn_flops / (attn_ms[0] * 1e-3) / 1e12, 1),
+                                 "switch_1_bf16_operands": round(attn_flops / (attn_ms[1] * 1e-3) / 1e12, 1)},
+            "rel_l2_on_vs_off": float((outs[1] - outs[0]).norm() / outs[0].norm()),
+            "finite": bool(torch.isfinite(outs[1]).all()), "device": torch.cuda.get_device_name(0)}
+
+
 def ragged(mode, steps, warmup, rows=16, shortest=3.0, longest=10.0):
     import time
 
@@ -233,9 +288,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None, help="append the JSON lines to this file as well")
     ap.add_argument("--ragged", action="store_true", help="the rows-of-unequal-length leg (base x 12 layers) instead")
+    ap.add_argument("--attn-bf16", action="store_true", help="bf16 mode with VCVITS_ATTN_STREAM_BF16 = 0 and 1 instead")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("hubert_bench: no GPU (there is no CPU path to time)")
+    if args.attn_bf16:
+        for arch in (args.arch.split(",") if args.arch != "base,xtralarge" else ["base"]):
+            line = json.dumps(attn_bf16(arch, args.batch, args.seconds, args.steps, args.warmup))
+            print(line, flush=True)
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(line + "\n")
+            torch.cuda.empty_cache()
+        return 0
     if args.ragged:
         for mode in args.modes.split(","):
             line = json.dumps(ragged(mode, args.steps, args.warmup))

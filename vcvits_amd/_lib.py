@@ -114,6 +114,7 @@ EXPORTS = [
     "vcv_hubert_groupnorm_gelu_len", "vcv_hubert_mask_frames", "vcv_hubert_attn_fwd_len",
     "vcv_rel_attn_stream_supported", "vcv_rel_attn_stream_fwd",
     "vcv_rel_attn_stream_train_fwd", "vcv_rel_attn_stream_bwd_workspace", "vcv_rel_attn_stream_bwd",
+    "vcv_rel_attn_stream_fwd_bf16", "vcv_hubert_attn_fwd_bf16", "vcv_hubert_attn_fwd_len_bf16",
 ]
 
 
@@ -257,11 +258,14 @@ _ARGTYPES = {
     "vcv_hubert_layernorm_c_gelu": [_P, _P, _P, _P, _I, _I, _I, _F, _P],
     "vcv_hubert_attn_supported": [_I, _I, _I, _I],
     "vcv_hubert_attn_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _L, _F, _P],
+    "vcv_hubert_attn_fwd_bf16": [_P, _P, _P, _P, _I, _I, _I, _I, _L, _F, _P],
     "vcv_hubert_groupnorm_gelu_len": [_P, _P, _P, _P, _I, _I, _I, _P, _F, _P],
     "vcv_hubert_mask_frames": [_P, _P, _I, _I, _I, _P, _P],
     "vcv_hubert_attn_fwd_len": [_P, _P, _P, _P, _I, _I, _I, _I, _L, _F, _P, _P],
+    "vcv_hubert_attn_fwd_len_bf16": [_P, _P, _P, _P, _I, _I, _I, _I, _L, _F, _P, _P],
     "vcv_rel_attn_stream_supported": [_I, _I, _I, _I, _I],
     "vcv_rel_attn_stream_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
+    "vcv_rel_attn_stream_fwd_bf16": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
     "vcv_rel_attn_stream_train_fwd": [_P] * 8 + [_I] * 5 + [_F, _F, ctypes.c_uint64, _P],
     "vcv_rel_attn_stream_bwd_workspace": [_I, _I, _I, _I, _I],
     "vcv_rel_attn_stream_bwd": [_P] * 15 + [_I] * 5 + [_F, _F, ctypes.c_uint64, _P],

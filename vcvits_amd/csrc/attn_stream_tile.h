@@ -13,6 +13,10 @@
 // The same map gives the channel of register r of an output tile o[j]: j * 32 + acc_row(r, hf).
 // LDS: Ks[D * 32] is [d][key]; Vs is [d][TILE_VS] with TILE_VS = 33, because the A fragments of the second product walk d
 // across the 32 lanes of a half at one key: a stride of 32 would put them all in one bank, 33 gives each its own.
+//
+// The bf16-operand form of the same frame (attention_stream_bf16.hip) is the second half of this file: the *_bf16 functions
+// replace the three that touch operands, everything else above is shared as it is.  Its LDS images and their strides are
+// described there.
 #pragma once
 #include "common.h"
 #include <math.h>
@@ -108,4 +112,116 @@ __device__ __forceinline__ void tile_store(float* __restrict__ out, size_t obase
       const int d = j * 32 + acc_row(r, hf);
       if (d < D) out[obase + (size_t)d * T + t] = live ? o[j][r] * inv : 0.f;
     }
+}
+
+// =====================================================================================================================
+// bf16 operands (attention_stream_bf16.hip): the same block, tiles, lane layout and streamed softmax, with both
+// contractions on v_mfma_f32_32x32x16_bf16.  K, V and Q are rounded to bf16 (nearest even) on the way in, the probabilities
+// on the way into the second product; scores, max, sum, alpha and the output accumulate in fp32 as above.
+//   S^T = K Q: D / 16 MFMAs.  A = 8 channels 16 * step + 8 * hf + e of key lane & 31, B = the same 8 channels of the lane's
+//   query, packed bf16 and UNSCALED (D / 4 registers); the scale multiplies the fp32 score, so bf16 inputs give the exact
+//   products whatever the scale.
+//   O += V P^T: the C/D layout is the fp32 one, so registers 8 m .. 8 m + 7 of S, cast to bf16, are the B fragment of MFMA
+//   m (m = 0, 1) of each 32-channel output tile: reduction element 8 * hf + e of MFMA m is key acc_row(8 m + e, hf), i.e. the
+//   two 4-key runs 16 m + 4 hf .. + 3 and 16 m + 8 + 4 hf .. + 3, which is what the A fragment reads from the value tile.
+// LDS: Ks is [key][TILE_KS(D)] bf16, channel innermost, so an A fragment of the scores is one 16-byte read.  TILE_KS = D + 8:
+// ds_read_b128 serves 16 lanes per cycle (keys that are distinct mod 16, one half), each 4 dwords wide; the row stride is
+// D / 2 + 4 dwords, which is 4 mod 8 for D = 32, 64, 80, so key * stride walks the 16 four-dword bank groups of the 64 banks
+// once: conflict-free, and rows stay 16-byte aligned.  An unpadded D / 2 would put every key of D = 64 on the same banks.
+// Vs is [channel][TILE_VSB] bf16, key innermost, so an A fragment of the second product is two 8-byte reads.  TILE_VSB = 36:
+// ds_read_b64 serves the 32 channels of a half per cycle at one key offset, 2 dwords each; the stride of 18 dwords is 2 mod
+// 4, so channel * 18 walks the 32 two-dword bank pairs once (16 dwords, the unpadded tile, would hit each pair twice over).
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+constexpr int TILE_VSB = 36;                                   // row stride of the bf16 value tile, in elements
+constexpr int tile_ks(int D) { return D + 8; }                 // row stride of the bf16 key tile, in elements
+
+// qf[8 i + e] = q[16 i + 8 hf + e][t] in fp32 and unscaled: the channels of the lane's B fragments; 0 where the query does
+// not exist (one branch around all the loads, as tile_load_q)
+template <int D>
+__device__ __forceinline__ void tile_load_q_bf16(float (&qf)[D / 2], const float* __restrict__ q, size_t base, int T, int t,
+                                                 int hf, bool ok) {
+#pragma unroll
+  for (int i = 0; i < D / 2; ++i) qf[i] = 0.f;
+  if (ok)
+#pragma unroll
+    for (int i = 0; i < D / 2; ++i) qf[i] = q[base + (size_t)(16 * (i >> 3) + 8 * hf + (i & 7)) * T + t];
+}
+
+// the lane's B operands of every score product: qf rounded to bf16, D / 4 registers
+template <int D>
+__device__ __forceinline__ void tile_pack_q_bf16(bf16x8 (&qb)[D / 16], const float (&qf)[D / 2]) {
+#pragma unroll
+  for (int i = 0; i < D / 16; ++i)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) qb[i][e] = (__bf16)qf[8 * i + e];
+}
+
+// keys / values s0 .. s0 + 31 of the head at `base`, rounded to bf16, into Ks ([key][channel]) / Vs ([channel][key]) by
+// all 256 threads: a thread is one key and D / 8 adjacent channels, so its keys leave as one packed run.  Keys at or past n
+// are staged as 0 by a select and never read from memory.  The caller puts the block's barriers around it.
+template <int D>
+__device__ __forceinline__ void tile_stage_kv_bf16(__bf16* Ks, __bf16* Vs, const float* __restrict__ k,
+                                                   const float* __restrict__ v, size_t base, int T, int s0, int n, int tid) {
+  constexpr int CH = D / 8, KS = tile_ks(D);
+  const int sc = tid & 31, c0 = (tid >> 5) * CH;
+  const int s = s0 + sc;
+  const bool sok = s < n;
+  __bf16 kk[CH];
+#pragma unroll
+  for (int i = 0; i < CH; ++i) {
+    const size_t g = base + (size_t)(c0 + i) * T + (sok ? s : 0);
+    kk[i] = (__bf16)(sok ? k[g] : 0.f);
+    Vs[(c0 + i) * TILE_VSB + sc] = (__bf16)(sok ? v[g] : 0.f);
+  }
+  __bf16* kd = Ks + sc * KS + c0;
+  if constexpr (CH == 8) {
+    bf16x8 w;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w[i] = kk[i];
+    *reinterpret_cast<bf16x8*>(kd) = w;  // 16 * (9 sc + sd) bytes into the tile
+  } else if constexpr (CH == 4) {
+    bf16x4 w = {kk[0], kk[1], kk[2], kk[3]};
+    *reinterpret_cast<bf16x4*>(kd) = w;  // 8 * (10 sc + sd) bytes
+  } else {
+#pragma unroll
+    for (int i = 0; i < CH; i += 2) {
+      bf16x2 w = {kk[i], kk[i + 1]};
+      *reinterpret_cast<bf16x2*>(kd + i) = w;  // CH is even: 4-byte aligned
+    }
+  }
+}
+
+// S^T = scale * (K Q) for the tile in Ks
+template <int D>
+__device__ __forceinline__ f32x16 tile_scores_bf16(const __bf16* Ks, const bf16x8 (&qb)[D / 16], float scale, int col, int hf) {
+  f32x16 S = {};
+#pragma unroll
+  for (int i = 0; i < D / 16; ++i) {
+    const bf16x8 a = *reinterpret_cast<const bf16x8*>(Ks + col * tile_ks(D) + 16 * i + 8 * hf);
+    S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qb[i], S, 0, 0, 0);
+  }
+  return S * scale;
+}
+
+// o = o * alpha + V P^T for the tile in Vs (DT * 32 rows) and the probabilities in S, rounded to bf16 here and only here
+template <int DT>
+__device__ __forceinline__ void tile_pv_bf16(f32x16 (&o)[DT], const __bf16* Vs, const f32x16& S, float alpha, int col, int hf) {
+#pragma unroll
+  for (int j = 0; j < DT; ++j) o[j] *= alpha;
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    bf16x8 b;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) b[e] = (__bf16)S[8 * m + e];
+#pragma unroll
+    for (int j = 0; j < DT; ++j) {
+      const __bf16* vr = Vs + (j * 32 + col) * TILE_VSB + 16 * m + 4 * hf;  // key acc_row(8 m, hf)
+      const bf16x4 lo = *reinterpret_cast<const bf16x4*>(vr), hi = *reinterpret_cast<const bf16x4*>(vr + 8);
+      const bf16x8 a = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+      o[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, o[j], 0, 0, 0);
+    }
+  }
 }

@@ -140,15 +140,29 @@ _ATTN_STREAM_MIN_T = [tuning.integer("VCVITS_ATTN_STREAM_MIN_T", 897, "shortest 
                                      "runs on the streamed kernel (memory linear in T; 0: never)")]
 
 
+# bf16 compute mode: the streamed forward kernels (this one and HuBERT's, ops.hubert) with bf16 operands on the bf16 matrix
+# pipe (attention_stream_bf16.hip); 0 (the default): bf16 mode keeps the fp32-operand kernels and their bits
+_ATTN_STREAM_BF16 = [tuning.integer("VCVITS_ATTN_STREAM_BF16", 0, "bf16 mode: streamed attention (relative-position at long T, HuBERT) "
+                                    "with bf16 operands on the bf16 matrix pipe (0: fp32 operands in both modes)")]
+
+
+def attn_stream_bf16():
+    """True when a streamed attention call goes to the bf16-operand kernels: the switch is 1 and the compute dtype is bf16."""
+    return _ATTN_STREAM_BF16[0] == 1 and _COMPUTE[0] == "bf16"
+
+
 def _rel_attn_stream(q, k, v, embk, embv, mask, n_heads, window):
-    """One launch of vcv_rel_attn_stream_fwd: out [B, C, T], nothing of size T x T allocated."""
+    """One launch of vcv_rel_attn_stream_fwd (or of its bf16-operand twin, see attn_stream_bf16): out [B, C, T], nothing of
+    size T x T allocated."""
     q, k, v, embk, embv, mask = (_f32c(t) for t in (q, k, v, embk, embv, mask))
     B, C, T = q.shape
     dk = C // n_heads
     out = torch.empty_like(q)
-    check(lib().vcv_rel_attn_stream_fwd(ptr(q), ptr(k), ptr(v), ptr(embk), ptr(embv), ptr(mask), ptr(out), B, n_heads, dk, T,
-                                        window, 1.0 / (dk ** 0.5), stream()), "vcv_rel_attn_stream_fwd")
-    LAUNCH_COUNTS["attn_stream"] += 1
+    bf = attn_stream_bf16()
+    name = "vcv_rel_attn_stream_fwd_bf16" if bf else "vcv_rel_attn_stream_fwd"
+    check(getattr(lib(), name)(ptr(q), ptr(k), ptr(v), ptr(embk), ptr(embv), ptr(mask), ptr(out), B, n_heads, dk, T,
+                               window, 1.0 / (dk ** 0.5), stream()), name)
+    LAUNCH_COUNTS["attn_stream_bf16" if bf else "attn_stream"] += 1
     return out
 
 

@@ -79,7 +79,7 @@ _COMPUTE = ["f32"]
 
 # which kernel family each GEMM-shaped launch went to (tests assert that the bf16 path really ran)
 LAUNCH_COUNTS = {"bf16": 0, "bf16io": 0, "x3": 0, "pk": 0, "dma": 0, "gemm": 0, "wgrad_bf16": 0, "wgrad_x3": 0, "wgrad": 0,
-                 "attn_fused": 0, "attn_stream": 0, "attn_stream_grad": 0}
+                 "attn_fused": 0, "attn_stream": 0, "attn_stream_grad": 0, "attn_stream_bf16": 0}
 
 
 # bf16 mode stores the conv <-> conv activations of the decoder's inference pass in bf16 in HBM (vcv_conv_bf16io_*: what the

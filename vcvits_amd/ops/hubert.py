@@ -16,6 +16,8 @@ import ctypes
 import torch
 
 from .._lib import check, lib, ptr, stream
+from .core import LAUNCH_COUNTS
+from .attention import attn_stream_bf16
 
 HUBERT_HEAD_DIMS = (64, 80)
 
@@ -42,12 +44,19 @@ def hubert_attention_supported(B, H, head_dim, T):
 
 
 def _attn_launch(q, k, v, out, B, n_heads, d, T, ldb, scale, lengths):
+    """The fp32-operand kernels, or in bf16 mode with VCVITS_ATTN_STREAM_BF16 = 1 (attn_stream_bf16) their bf16-operand twins,
+    which count as "attn_stream_bf16" in LAUNCH_COUNTS."""
     scale = float(d) ** -0.5 if scale is None else float(scale)
+    bf = attn_stream_bf16()
     if lengths is None:
-        check(lib().vcv_hubert_attn_fwd(q, k, v, ptr(out), B, n_heads, d, T, ldb, scale, stream()), "vcv_hubert_attn_fwd")
+        name = "vcv_hubert_attn_fwd_bf16" if bf else "vcv_hubert_attn_fwd"
+        check(getattr(lib(), name)(q, k, v, ptr(out), B, n_heads, d, T, ldb, scale, stream()), name)
     else:
-        check(lib().vcv_hubert_attn_fwd_len(q, k, v, ptr(out), B, n_heads, d, T, ldb, scale,
-                                            ptr(_hb_lengths(lengths, B, "lengths")), stream()), "vcv_hubert_attn_fwd_len")
+        name = "vcv_hubert_attn_fwd_len_bf16" if bf else "vcv_hubert_attn_fwd_len"
+        check(getattr(lib(), name)(q, k, v, ptr(out), B, n_heads, d, T, ldb, scale,
+                                   ptr(_hb_lengths(lengths, B, "lengths")), stream()), name)
+    if bf:
+        LAUNCH_COUNTS["attn_stream_bf16"] += 1
     return out
 
 
