@@ -6,7 +6,8 @@
 // The frame is the one of attn_stream_tile.h (block = one head x 128 lanes-as-columns, tiles of 32 rows through LDS, both
 // contractions on v_mfma_f32_32x32x2_f32, __expf); the maths is tests/attention_f64.py points 1-5.
 //
-//   rel_attn_stream_train_fwd_kernel<D>  the streamed forward of attention_stream.hip plus
+//   rel_attn_stream_train_fwd_kernel<D>  the streamed forward of attention_stream.hip -- the same body,
+//   rel_attn_stream_fwd_body of attn_stream_fwd.h, not a copy of it -- with TrainHook (below) for
 //     * dropout: the running sum l takes exp(s - m) as it is, the value product and the band entries take it times
 //       drop_scale(seed, (g*T + i)*T + j): the generator and the flat index of attention.hip, so the fused kernels, the
 //       unfused path and tests/attention_f64.keep_mask all draw the same mask.  p = 0 is one uniform branch;
@@ -37,7 +38,7 @@
 //
 // Resources (hipcc -O3, gfx950, from the code object's metadata; tests/test_attention_stream_grad_cpu.py reads them):
 //   kernel, dk            registers (vector + accumulation, unified)   SGPR   static LDS
-//   train_fwd  32 / 64    220 / 288                                    99     30,976 / 43,392 B
+//   train_fwd  32 / 64    220 / 288                                    100    30,976 / 43,392 B
 //   bwd_q      32 / 64    216 / 291                                    88/89  49,536 / 62,080 B
 //   bwd_kv     32 / 64    276 / 348                                    52     8,960 / 17,408 B
 //   demb_reduce           12                                           20     4,160 B
@@ -46,12 +47,10 @@
 // What keeps the scalar registers from spilling, and is easy to undo by accident: 16 selects in a row hold 16 lane masks
 // (32 scalar registers) between the compares and their uses.  So the dropout factor is applied as a bit mask and not as a
 // select (drop_mix), and the query pass does not test `key < T` per element (see there).
-#include "attn_stream_tile.h"
+#include "attn_stream_fwd.h"
 
 namespace {
 
-constexpr int RELS = 16;  // relative positions at most (2w + 1 <= 16)
-constexpr int RS = 18;    // row stride of the band tables (attention_stream.hip)
 constexpr int LS = 33;    // row stride of a tile that is read both along and across its rows
 
 // The dropout mask of attention.hip / vits_blocks.hip: same stream, same masks.  There the factor of element idx is
@@ -125,123 +124,41 @@ __device__ __forceinline__ void acc_tile(f32x16 (&o)[DT], const float* Xs, const
   }
 }
 
+// The training forward's two additions to rel_attn_stream_fwd_body (attn_stream_fwd.h): dropout on the probabilities of a
+// tile -- the row sum l has taken exp(s - m) as it is, the band entries and the value product take it dropped -- and the
+// stats pair of a query at the end.  p = 0 is one uniform branch, and then the bits are the plain streamed forward's.
+struct TrainHook {
+  float* __restrict__ stats;
+  int T;
+  float pdrop, inv_keep;
+  unsigned long long seed;
+  __device__ __forceinline__ void tile(f32x16& S, int s0, int i, int hf) const {
+    if (pdrop > 0.f) {
+      const size_t drow = ((size_t)blockIdx.y * T + i) * T;  // flat index of this query's first probability
+      float c[16];
+      drop_tile(c, seed, drow + (size_t)(s0 + 4 * hf), 1ull, pdrop, inv_keep);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) S[r] *= c[r];
+    }
+  }
+  __device__ __forceinline__ void done(int t, int hf, float m, float l) const {
+    if (hf == 0) {
+      const size_t si = ((size_t)blockIdx.y * T + t) * 2;
+      stats[si] = m;
+      stats[si + 1] = l;
+    }
+  }
+};
+
 template <int D>
 __global__ void __launch_bounds__(256)
 rel_attn_stream_train_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                  const float* __restrict__ embk, const float* __restrict__ embv, const float* __restrict__ mask,
                                  float* __restrict__ out, float* __restrict__ stats, int H, int T, int w, float qscale,
                                  float pdrop, unsigned long long seed, const unsigned long long* __restrict__ seed_off) {
-  constexpr int DT = D / 32;
-  __shared__ float Ks[D * 32];
-  __shared__ float Vs[D * TILE_VS];
-  __shared__ __attribute__((aligned(16))) float Ms[32];
-  __shared__ float Ek[RELS * D];
-  __shared__ float Ev[RELS * D];
-  __shared__ float Rl[128 * RS];  // rel[r] of the block's queries
-  __shared__ float Pb[128 * RS];  // un-normalised, dropped band probabilities
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int col = lane & 31, hf = lane >> 5;
-  const int nr = 2 * w + 1;
-  const size_t base = (size_t)blockIdx.y * D * T;
-  const size_t mbase = (size_t)(blockIdx.y / H) * T;
-  const int t0 = blockIdx.x * 128 + wv * 32;
-  const int t = t0 + col;
-  const bool tok = t < T;
-  const int row = (wv * 32 + col) * RS;
-  const float inv_keep = 1.f / (1.f - pdrop);
   if (seed_off) seed += *seed_off;
-  const size_t drow = ((size_t)blockIdx.y * T + (tok ? t : 0)) * T;  // flat index of this query's first probability
-
-  float qr[D / 2];
-  tile_load_q<D>(qr, q, base, T, t, hf, qscale, tok);
-  const float mi = tok ? mask[mbase + t] : 0.f;
-  for (int i = tid; i < RELS * D; i += 256) {
-    Ek[i] = i < nr * D ? embk[i] : 0.f;
-    Ev[i] = i < nr * D ? embv[i] : 0.f;
-  }
-  for (int i = tid; i < 128 * RS; i += 256) Pb[i] = 0.f;
-  __syncthreads();
-  for (int r = 0; r < nr; ++r) {
-    float a = 0.f;
-#pragma unroll
-    for (int i = 0; i < D / 2; ++i) a += qr[i] * Ek[r * D + 2 * i + hf];
-    a += __shfl_xor(a, 32);
-    if (hf == 0) Rl[row + r] = a;
-  }
-
-  f32x16 o[DT] = {};
-  float m = -INFINITY, l = 0.f;
-  float c0 = 0.f, c1 = 0.f, c2 = 0.f;  // rescale carried by the band entries of the tiles at t0 - 32, t0, t0 + 32
-
-  for (int s0 = 0; s0 < T; s0 += 32) {
-    __syncthreads();
-    tile_stage_kv<D>(Ks, Vs, k, v, base, T, s0, T, tid);
-    if (tid < 32) Ms[tid] = s0 + tid < T ? mask[mbase + s0 + tid] : 0.f;
-    __syncthreads();
-    f32x16 S = tile_scores<D>(Ks, qr, col, hf);
-
-    const int ds = s0 - t0;
-    const bool band = ds >= -32 && ds <= 32;  // wave-uniform
-    if (band) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int off = ds + acc_row(r, hf) - col + w;  // key - query + w
-        const bool inb = off >= 0 && off < nr;
-        const float rel = Rl[row + (inb ? off : 0)];
-        S[r] += inb ? rel : 0.f;
-      }
-    }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const float4 mj = *reinterpret_cast<const float4*>(&Ms[8 * g + 4 * hf]);
-      S[4 * g + 0] = mi * mj.x == 0.f ? -1e4f : S[4 * g + 0];
-      S[4 * g + 1] = mi * mj.y == 0.f ? -1e4f : S[4 * g + 1];
-      S[4 * g + 2] = mi * mj.z == 0.f ? -1e4f : S[4 * g + 2];
-      S[4 * g + 3] = mi * mj.w == 0.f ? -1e4f : S[4 * g + 3];
-    }
-    if (s0 + 32 > T) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        if (s0 + acc_row(r, hf) >= T) S[r] = -INFINITY;
-    }
-    const float alpha = tile_softmax_step<true>(S, m, l);  // l has taken the un-dropped exponentials
-    if (pdrop > 0.f) {
-      float c[16];
-      drop_tile(c, seed, drow + (size_t)(s0 + 4 * hf), 1ull, pdrop, inv_keep);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) S[r] *= c[r];
-    }
-    c0 *= alpha, c1 *= alpha, c2 *= alpha;
-    if (band) {
-      if (ds < 0) c0 = 1.f;
-      else if (ds == 0) c1 = 1.f;
-      else c2 = 1.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int sr = acc_row(r, hf);
-        const int off = ds + sr - col + w;
-        if (off >= 0 && off < nr && s0 + sr < T) Pb[row + off] = S[r];
-      }
-    }
-    tile_pv(o, Vs, S, alpha, col, hf);
-  }
-
-  __syncthreads();
-  if (!tok) return;
-  for (int r = 0; r < nr; ++r) {
-    const int rel = col + r - w;  // key - t0
-    const float p = Pb[row + r] * (rel < 0 ? c0 : rel < 32 ? c1 : c2);
-#pragma unroll
-    for (int j = 0; j < DT; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) o[j][e] += p * Ev[r * D + j * 32 + acc_row(e, hf)];
-  }
-  tile_store<D>(out, base, T, t, o, l, hf, true);
-  if (hf == 0) {
-    const size_t si = ((size_t)blockIdx.y * T + t) * 2;
-    stats[si] = m;
-    stats[si + 1] = l;
-  }
+  rel_attn_stream_fwd_body<TileF32<D>>(q, k, v, embk, embv, mask, out, H, T, w, qscale,
+                                       TrainHook{stats, T, pdrop, 1.f / (1.f - pdrop), seed});
 }
 
 // Query pass.

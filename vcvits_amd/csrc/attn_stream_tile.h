@@ -1,5 +1,8 @@
-// attn_stream_tile.h -- the frame shared by the two streamed-softmax attention kernels, hubert_attn_fwd_kernel (hubert.hip)
-// and rel_attn_stream_fwd_kernel (attention_stream.hip), as plain functions over the arrays those kernels declare.
+// attn_stream_tile.h -- the frame shared by the streamed-softmax attention kernels: the HuBERT forward (hubert.hip), the
+// relative-position forward (attention_stream.hip), its training form (attention_stream_grad.hip) and the bf16-operand forms
+// of the first two (attention_stream_bf16.hip).  This file holds the tile primitives, as plain functions over the arrays of
+// a kernel, and the two OPERAND POLICIES TileF32 / TileBF16 (end of file) that group them; attn_stream_fwd.h, beside it,
+// holds the two forward bodies, each written once over a policy, and their launchers.
 //
 // A block is one head and 128 queries: each of its 4 waves owns 32 queries for the whole launch and the block streams the
 // keys / values in TILES OF 32 KEYS through LDS; nothing of size T x T exists.  A head is D rows of T floats, T contiguous.
@@ -14,9 +17,8 @@
 // LDS: Ks[D * 32] is [d][key]; Vs is [d][TILE_VS] with TILE_VS = 33, because the A fragments of the second product walk d
 // across the 32 lanes of a half at one key: a stride of 32 would put them all in one bank, 33 gives each its own.
 //
-// The bf16-operand form of the same frame (attention_stream_bf16.hip) is the second half of this file: the *_bf16 functions
-// replace the three that touch operands, everything else above is shared as it is.  Its LDS images and their strides are
-// described there.
+// The bf16-operand form of the same frame is the second half of this file: the *_bf16 functions replace the three that
+// touch operands, everything else above is shared as it is.  Its LDS images and their strides are described there.
 #pragma once
 #include "common.h"
 #include <math.h>
@@ -225,3 +227,67 @@ __device__ __forceinline__ void tile_pv_bf16(f32x16 (&o)[DT], const __bf16* Vs, 
     }
   }
 }
+
+// =====================================================================================================================
+// Operand policies: what a forward body (attn_stream_fwd.h) takes as its template argument.  A policy is the LDS element type
+// and the shapes of the two tiles, the lane's score operand, the three functions that touch operands, which channel element i
+// of the lane's fp32 query view qf[D / 2] holds, and where the scale goes.  The functions above are the policies'
+// implementations: a forward body reaches them through its policy only (tile_load_q is the column loader of the backward
+// kernels of attention_stream_grad.hip as well).  Where the scale goes is part of each kernel's bits:
+//   TileF32   qf = q * scale on load; a band term rel[r] is the sum of qf . embk[r] as it is; the scores take no further scale.
+//   TileBF16  qf = q; rel[r] = (sum of qf . embk[r]) * scale, from the fp32 qf before it is packed; the fp32 score is
+//             multiplied by the scale after the MFMAs.
+template <int D_>
+struct TileF32 {
+  static constexpr int D = D_;
+  typedef float elem;
+  static constexpr int ALIGN = 4, KN = D * 32, VS = TILE_VS;  // of both tiles, in bytes; elements of Ks; row stride of Vs
+  typedef float qop[D / 2];
+  static __device__ __forceinline__ int chan(int i, int hf) { return 2 * i + hf; }
+  static __device__ __forceinline__ void load_q(float (&qf)[D / 2], const float* __restrict__ q, size_t base, int T, int t, int hf,
+                                                float scale, bool ok) {
+    tile_load_q<D>(qf, q, base, T, t, hf, scale, ok);
+  }
+  static __device__ __forceinline__ float rel_term(float sum, float) { return sum; }
+  static __device__ __forceinline__ void pack_q(qop& qo, const float (&qf)[D / 2]) {
+#pragma unroll
+    for (int i = 0; i < D / 2; ++i) qo[i] = qf[i];
+  }
+  static __device__ __forceinline__ void stage_kv(elem* Ks, elem* Vs, const float* __restrict__ k, const float* __restrict__ v,
+                                                  size_t base, int T, int s0, int n, int tid) {
+    tile_stage_kv<D>(Ks, Vs, k, v, base, T, s0, n, tid);
+  }
+  static __device__ __forceinline__ f32x16 scores(const elem* Ks, const qop& qo, float, int col, int hf) {
+    return tile_scores<D>(Ks, qo, col, hf);
+  }
+  template <int DT>
+  static __device__ __forceinline__ void pv(f32x16 (&o)[DT], const elem* Vs, const f32x16& S, float alpha, int col, int hf) {
+    tile_pv(o, Vs, S, alpha, col, hf);
+  }
+};
+
+template <int D_>
+struct TileBF16 {
+  static constexpr int D = D_;
+  typedef __bf16 elem;
+  static constexpr int ALIGN = 16, KN = 32 * tile_ks(D), VS = TILE_VSB;
+  typedef bf16x8 qop[D / 16];
+  static __device__ __forceinline__ int chan(int i, int hf) { return 16 * (i >> 3) + 8 * hf + (i & 7); }
+  static __device__ __forceinline__ void load_q(float (&qf)[D / 2], const float* __restrict__ q, size_t base, int T, int t, int hf,
+                                                float, bool ok) {
+    tile_load_q_bf16<D>(qf, q, base, T, t, hf, ok);
+  }
+  static __device__ __forceinline__ float rel_term(float sum, float scale) { return sum * scale; }
+  static __device__ __forceinline__ void pack_q(qop& qo, const float (&qf)[D / 2]) { tile_pack_q_bf16<D>(qo, qf); }
+  static __device__ __forceinline__ void stage_kv(elem* Ks, elem* Vs, const float* __restrict__ k, const float* __restrict__ v,
+                                                  size_t base, int T, int s0, int n, int tid) {
+    tile_stage_kv_bf16<D>(Ks, Vs, k, v, base, T, s0, n, tid);
+  }
+  static __device__ __forceinline__ f32x16 scores(const elem* Ks, const qop& qo, float scale, int col, int hf) {
+    return tile_scores_bf16<D>(Ks, qo, scale, col, hf);
+  }
+  template <int DT>
+  static __device__ __forceinline__ void pv(f32x16 (&o)[DT], const elem* Vs, const f32x16& S, float alpha, int col, int hf) {
+    tile_pv_bf16(o, Vs, S, alpha, col, hf);
+  }
+};

@@ -1,6 +1,7 @@
 // hubert.hip -- what HuBERT inference (vcvits_amd/model/hubert.py) needs beyond the conv family and layernorm_c:
 //   * softmax self-attention, forward only, keys / values streamed in tiles (no [T, T] tensor in memory), on the frame of
-//     attn_stream_tile.h that the streamed relative-position kernel (attention_stream.hip) shares;
+//     attn_stream_tile.h that the streamed relative-position kernels share; the kernel is hubert_attn_fwd_body of
+//     attn_stream_fwd.h with fp32 operands, the body attention_stream_bf16.hip instantiates with bf16 ones;
 //   * GroupNorm(C, C) over time fused with GELU (layer 0 of the base model's conv front end);
 //   * LayerNorm over channels fused with GELU (every layer of the large models' front end);
 //   * bias + exact GELU (+ residual) as one streaming pass.
@@ -15,7 +16,7 @@
 //   * vcv_hubert_attn_fwd_len        keys s < frames[b] only, exact 0 for the queries behind them.
 // All three select, never multiply: NaN or Inf behind a row's end does not reach a valid frame.  The entry points without
 // lengths are the same kernels instantiated without the array, with the instructions they had before it existed.
-#include "attn_stream_tile.h"
+#include "attn_stream_fwd.h"
 
 namespace {
 
@@ -150,59 +151,29 @@ hubert_layernorm_c_gelu_kernel(const float* x, const float* __restrict__ gamma, 
 }
 
 // ---- softmax((q * scale)^T k) v per head, forward only, on the streamed frame of attn_stream_tile.h (layout, tiles and
-// the two MFMA contractions are described there), with expf.  q / k / v / out: [B, H * D, T]; batch rows of q / k / v are
+// the two MFMA contractions are described there), with expf: hubert_attn_fwd_body<TileF32<D>, LEN> (attn_stream_fwd.h), which
+// the following describes.  q / k / v / out: [B, H * D, T]; batch rows of q / k / v are
 // `ldb` floats apart (H * D * T, or 3 * H * D * T when the three are slices of one fused projection).  Grid
 // (ceil(T / 128), B * H), 256 threads.  D = 80 pads the value tile to 96 rows of zeros (3 output tiles of 32 channels).
 // LEN: a head of batch row b sees the keys s < n = frames[b] only (precondition 1 <= frames[b] <= T, so key 0 exists; the
 // value is clamped into that range, so a bad one cannot read out of bounds).  The key loop ends at n, keys / values and
 // queries at or behind n are staged as 0 by a select (whatever is stored there, NaN included, is never used), their scores
 // are -inf, and the output of the queries t >= n is exact 0.  A block whose 128 queries all lie behind n writes its zeros
-// and leaves before the first barrier (n is uniform over the block).  Without LEN n is T and the code is what it was. ------
+// and leaves before the first barrier (n is uniform over the block).  Without LEN n is T and the code is what it was.
+// Resources (hipcc -O3, gfx950, from the code object's metadata; tests/test_attention_stream_cpu.py holds them): D = 64: 192
+// registers, 51 / 55 SGPR without / with LEN, 16,640 B LDS; D = 80: 248 registers, 52 / 55 SGPR, 22,912 B LDS; 0 B scratch,
+// no spills. ------
 template <int D, bool LEN>
 __global__ void __launch_bounds__(256)
 hubert_attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                        float* __restrict__ out, int H, int T, size_t ldb, float scale, const int* __restrict__ frames) {
-  constexpr int DT = (D + 31) / 32;  // output tiles of 32 channels
-  __shared__ float Ks[D * 32];
-  __shared__ float Vs[DT * 32 * TILE_VS];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int col = lane & 31, hf = lane >> 5;
-  const size_t base = (size_t)(blockIdx.y / H) * ldb + (size_t)(blockIdx.y % H) * D * T;
-  const size_t obase = (size_t)blockIdx.y * D * T;
-  const int t = blockIdx.x * 128 + wv * 32 + col;
-  const bool tok = t < T;
-  int n = T;  // keys (and queries) that exist
-  if (LEN) {
-    n = min(max(frames[blockIdx.y / H], 1), T);
-    if ((int)blockIdx.x * 128 >= n) {
-      if (tok)
-#pragma unroll
-        for (int i = 0; i < D / 2; ++i) out[obase + (size_t)(2 * i + hf) * T + t] = 0.f;
-      return;
-    }
-  }
-  const bool qok = t < n;
-
-  float qr[D / 2];
-  tile_load_q<D>(qr, q, base, T, t, hf, scale, qok);
-  for (int i = D * TILE_VS + tid; i < DT * 32 * TILE_VS; i += 256) Vs[i] = 0.f;
-  f32x16 o[DT] = {};
-  float m = -INFINITY, l = 0.f;
-
-  for (int s0 = 0; s0 < n; s0 += 32) {
-    __syncthreads();  // the previous tile has been read
-    tile_stage_kv<D>(Ks, Vs, k, v, base, T, s0, n, tid);
-    __syncthreads();
-    f32x16 S = tile_scores<D>(Ks, qr, col, hf);
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      if (s0 + acc_row(r, hf) >= n) S[r] = -INFINITY;
-    const float alpha = tile_softmax_step<false>(S, m, l);
-    tile_pv(o, Vs, S, alpha, col, hf);
-  }
-
-  if (tok) tile_store<D>(out, obase, T, t, o, l, hf, !LEN || qok);
+  hubert_attn_fwd_body<TileF32<D>, LEN>(q, k, v, out, H, T, ldb, scale, frames);
 }
+
+struct HubertFwdF32 {
+  template <int D, bool LEN>
+  static auto kernel() { return hubert_attn_fwd_kernel<D, LEN>; }
+};
 
 }  // namespace
 
@@ -258,22 +229,12 @@ extern "C" int vcv_hubert_attn_supported(int B, int H, int dk, int T) {
   return (dk == 64 || dk == 80) ? 0 : 1;
 }
 
-// frames: null launches the kernel without lengths
-static int attn_fwd_launch(const float* q, const float* k, const float* v, float* out, int B, int H, int dk, int T,
-                           int64_t ldb, float scale, const int* frames, void* stream) {
-  if (!q || !k || !v || !out || vcv_hubert_attn_supported(B, H, dk, T) != 0 || ldb < (int64_t)H * dk * T) return VCV_EINVAL;
-  const auto kernel = dk == 64 ? (frames ? hubert_attn_fwd_kernel<64, true> : hubert_attn_fwd_kernel<64, false>)
-                               : (frames ? hubert_attn_fwd_kernel<80, true> : hubert_attn_fwd_kernel<80, false>);
-  kernel<<<dim3(vcv_cdiv(T, 128), B * H), 256, 0, (hipStream_t)stream>>>(q, k, v, out, H, T, (size_t)ldb, scale, frames);
-  return vcv_check_launch();
-}
-
 extern "C" int vcv_hubert_attn_fwd(const float* q, const float* k, const float* v, float* out, int B, int H, int dk, int T,
                                    int64_t ldb, float scale, void* stream) {
-  return attn_fwd_launch(q, k, v, out, B, H, dk, T, ldb, scale, nullptr, stream);
+  return hubert_attn_launch<HubertFwdF32>(q, k, v, out, B, H, dk, T, ldb, scale, nullptr, stream);
 }
 
 extern "C" int vcv_hubert_attn_fwd_len(const float* q, const float* k, const float* v, float* out, int B, int H, int dk, int T,
                                        int64_t ldb, float scale, const int* frames, void* stream) {
-  return frames ? attn_fwd_launch(q, k, v, out, B, H, dk, T, ldb, scale, frames, stream) : VCV_EINVAL;
+  return frames ? hubert_attn_launch<HubertFwdF32>(q, k, v, out, B, H, dk, T, ldb, scale, frames, stream) : VCV_EINVAL;
 }
