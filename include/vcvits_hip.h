@@ -459,7 +459,10 @@ int vcv_stft_mag_bwd(const float* y, const float* window, const float* twiddle, 
 
 /* ---- WaveNet block glue (modules.py:147-175; gate = commons.py:99-106) ----
  * xin [B,2H,T]; g = cond_layer output viewed [B, gstride] (NULL when no speaker conditioning),
- * layer slice at goff; acts [B,H,T] = tanh(xin[:, :H]+g[:H]) * sigmoid(xin[:, H:]+g[H:]). */
+ * layer slice at goff; acts [B,H,T] = tanh(xin[:, :H]+g[:H]) * sigmoid(xin[:, H:]+g[H:]).
+ * Every launcher of this section and of the split / coupling / KL / nearest / slice sections below returns VCV_EINVAL,
+ * before any launch or memset, for a null required pointer and for a dimension (B, H / C, T, R, Tin, Tout, S, n) that is
+ * not positive.  The gate also refuses g != NULL with goff < 0 or goff + 2H > gstride (the slice leaves the row of g). */
 int vcv_wn_gate_fwd(const float* xin, const float* g, int gstride, int goff, float* acts, int B, int H, int T,
                     void* stream);
 int vcv_wn_gate_bwd(const float* xin, const float* g, int gstride, int goff, const float* dacts, float* dxin,
@@ -510,6 +513,8 @@ int vcv_rel_softmax_fwd(const float* S, const float* q, const float* embk, const
                         uint64_t seed, void* stream);
 int vcv_rel_value_fwd(const float* P, const float* embv, float* out, int B, int H, int dk, int T, int w,
                       void* stream);
+/* VCV_EINVAL for a null pointer, a dimension that is not positive, w < 0, 2w+1 > 16 or dk > 128: decided before dembk / dembv
+ * are zeroed, so a refused call leaves them untouched. */
 int vcv_rel_softmax_bwd(const float* P, const float* Pd, float* dP, const float* dO, const float* q,
                         const float* embk, const float* embv, const float* mask, float* dSt, float* dqband,
                         float* dembk, float* dembv, int B, int H, int dk, int T, int w, float qscale,

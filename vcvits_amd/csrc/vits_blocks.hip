@@ -27,6 +27,12 @@ __device__ __forceinline__ float wmax_all(float s) {
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 inline dim3 g1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
+// every dimension of a launch is positive: a negative one would make the size_t product behind g1() an arbitrary grid
+inline bool pos(int a, int b = 1, int c = 1) { return a > 0 && b > 0 && c > 0; }
+// the gate reads g[b, goff .. goff + 2H) of a row of gstride floats
+inline bool gate_slice_ok(const float* g, int gstride, int goff, int H) {
+  return !g || (goff >= 0 && (long long)goff + 2ll * H <= (long long)gstride);
+}
 
 // counter-based dropout mask: scale 1/(1-p) with probability 1-p, else 0 (stateless, so forward,
 // backward and the transposed copy of a tensor all regenerate the same mask from (seed, index))
@@ -699,16 +705,16 @@ __global__ __launch_bounds__(256) void embedding_t_bwd_kernel(const long long* _
 
 extern "C" int vcv_wn_gate_fwd(const float* xin, const float* g, int gstride, int goff, float* acts, int B,
                                int H, int T, void* stream) {
+  if (!xin || !acts || !pos(B, H, T) || !gate_slice_ok(g, gstride, goff, H)) return VCV_EINVAL;
   const size_t n = (size_t)B * H * T;
-  if (!xin || !acts || n == 0) return VCV_EINVAL;
   hipLaunchKernelGGL(wn_gate_fwd_kernel, g1(n), dim3(256), 0, ST, xin, g, gstride, goff, acts, H, T, n);
   return vcv_check_launch();
 }
 
 extern "C" int vcv_wn_gate_bwd(const float* xin, const float* g, int gstride, int goff, const float* dacts,
                                float* dxin, int B, int H, int T, void* stream) {
+  if (!xin || !dacts || !dxin || !pos(B, H, T) || !gate_slice_ok(g, gstride, goff, H)) return VCV_EINVAL;
   const size_t n = (size_t)B * H * T;
-  if (!xin || !dacts || !dxin || n == 0) return VCV_EINVAL;
   hipLaunchKernelGGL(wn_gate_bwd_kernel, g1(n), dim3(256), 0, ST, xin, g, gstride, goff, dacts, dxin, H, T, n);
   return vcv_check_launch();
 }
@@ -723,7 +729,7 @@ extern "C" int vcv_row_sum(const float* x, float* out, int R, int T, int inner, 
 extern "C" int vcv_wn_res_skip_fwd(const float* x, const float* out, const float* rs, const float* mask,
                                    float* xn, float* on, int B, int H, int T, int last, void* stream) {
   const size_t n = (size_t)B * H * T;
-  if (!rs || !on || n == 0 || (!last && (!x || !mask || !xn))) return VCV_EINVAL;
+  if (!rs || !on || !pos(B, H, T) || (!last && (!x || !mask || !xn))) return VCV_EINVAL;
   hipLaunchKernelGGL(wn_res_skip_fwd_kernel, g1(n), dim3(256), 0, ST, x, out, rs, mask, xn, on, H, T, last, n);
   return vcv_check_launch();
 }
@@ -731,7 +737,7 @@ extern "C" int vcv_wn_res_skip_fwd(const float* x, const float* out, const float
 extern "C" int vcv_wn_res_skip_bwd(const float* dxn, const float* don, const float* mask, float* drs, float* dx,
                                    int B, int H, int T, void* stream) {
   const size_t n = (size_t)B * H * T;
-  if (!mask || !drs || !dx || n == 0) return VCV_EINVAL;
+  if (!mask || !drs || !dx || !pos(B, H, T)) return VCV_EINVAL;
   hipLaunchKernelGGL(wn_res_skip_bwd_kernel, g1(n), dim3(256), 0, ST, dxn, don, mask, drs, dx, H, T, n);
   return vcv_check_launch();
 }
@@ -739,7 +745,7 @@ extern "C" int vcv_wn_res_skip_bwd(const float* dxn, const float* don, const flo
 extern "C" int vcv_split_sample_fwd(const float* stats, const float* eps, const float* mask, float* m,
                                     float* logs, float* z, int B, int C, int T, void* stream) {
   const size_t n = (size_t)B * C * T;
-  if (!stats || !mask || !m || !logs || n == 0 || (eps && !z)) return VCV_EINVAL;
+  if (!stats || !mask || !m || !logs || !pos(B, C, T) || (eps && !z)) return VCV_EINVAL;
   hipLaunchKernelGGL(split_sample_fwd_kernel, g1(n), dim3(256), 0, ST, stats, eps, mask, m, logs, z, C, T, n);
   return vcv_check_launch();
 }
@@ -748,7 +754,7 @@ extern "C" int vcv_split_sample_bwd(const float* dm, const float* dlogs, const f
                                     const float* logs, const float* mask, float* dstats, int B, int C, int T,
                                     void* stream) {
   const size_t n = (size_t)B * C * T;
-  if (!mask || !dstats || n == 0 || (dz && eps && !logs)) return VCV_EINVAL;
+  if (!mask || !dstats || !pos(B, C, T) || (dz && eps && !logs)) return VCV_EINVAL;
   hipLaunchKernelGGL(split_sample_bwd_kernel, g1(n), dim3(256), 0, ST, dm, dlogs, dz, eps, logs, mask, dstats,
                      C, T, n);
   return vcv_check_launch();
@@ -757,7 +763,7 @@ extern "C" int vcv_split_sample_bwd(const float* dm, const float* dlogs, const f
 extern "C" int vcv_coupling(const float* x1, const float* m, const float* mask, float* y, int B, int C, int T,
                             int reverse, void* stream) {
   const size_t n = (size_t)B * C * T;
-  if (!x1 || !m || !mask || !y || n == 0) return VCV_EINVAL;
+  if (!x1 || !m || !mask || !y || !pos(B, C, T)) return VCV_EINVAL;
   hipLaunchKernelGGL(coupling_kernel, g1(n), dim3(256), 0, ST, x1, m, mask, y, C, T, reverse, n);
   return vcv_check_launch();
 }
@@ -943,12 +949,13 @@ extern "C" int vcv_rel_softmax_bwd(const float* P, const float* Pd, float* dP, c
                                    const float* embk, const float* embv, const float* mask, float* dSt,
                                    float* dqband, float* dembk, float* dembv, int B, int H, int dk, int T, int w,
                                    float qscale, void* stream) {
-  if (!P || !Pd || !dP || !dO || !q || !embk || !embv || !mask || !dSt || !dqband || !dembk || !dembv || 2 * w + 1 > 32)
+  if (!P || !Pd || !dP || !dO || !q || !embk || !embv || !mask || !dSt || !dqband || !dembk || !dembv)
     return VCV_EINVAL;
+  // (every refusal comes before the two tables are zeroed: a refused call leaves them as they were)
+  if (!pos(B, H, dk) || T <= 0 || w < 0 || 2 * w + 1 > RS_NRMAX || dk > 64 * RS_DD) return VCV_EINVAL;
   const size_t ne = sizeof(float) * (2 * w + 1) * dk;
   if (vcv_zero_async(dembk, ne, ST) != hipSuccess) return VCV_EHIP;
   if (vcv_zero_async(dembv, ne, ST) != hipSuccess) return VCV_EHIP;
-  if (2 * w + 1 > RS_NRMAX || dk > 64 * RS_DD) return VCV_EINVAL;
   hipLaunchKernelGGL(rel_softmax_bwd_kernel, dim3(vcv_cdiv(T, RS_ROWS), B * H), dim3(64), 0, ST, P, Pd, dP, dO, q, embk, embv, mask, dSt,
                      dqband, dembk, dembv, H, dk, T, w, qscale);
   return vcv_check_launch();
@@ -957,7 +964,7 @@ extern "C" int vcv_rel_softmax_bwd(const float* P, const float* Pd, float* dP, c
 extern "C" int vcv_kl_fwd(const float* zp, const float* lq, const float* mp, const float* lp, const float* mask,
                           float* out2, int B, int C, int T, void* stream) {
   const size_t n = (size_t)B * C * T;
-  if (!zp || !lq || !mp || !lp || !mask || !out2 || n == 0) return VCV_EINVAL;
+  if (!zp || !lq || !mp || !lp || !mask || !out2 || !pos(B, C, T)) return VCV_EINVAL;
   if (vcv_zero_async(out2, 2 * sizeof(float), ST) != hipSuccess) return VCV_EHIP;
   size_t nb = (n + 2047) / 2048;
   if (nb > 1024) nb = 1024;
@@ -972,7 +979,7 @@ extern "C" int vcv_kl_bwd(const float* zp, const float* mp, const float* lp, con
                           const float* den, float* dzp, float* dlq, float* dmp, float* dlp, int B, int C, int T,
                           void* stream) {
   const size_t n = (size_t)B * C * T;
-  if (!zp || !mp || !lp || !mask || !gout || !den || !dzp || !dlq || !dmp || !dlp || n == 0) return VCV_EINVAL;
+  if (!zp || !mp || !lp || !mask || !gout || !den || !dzp || !dlq || !dmp || !dlp || !pos(B, C, T)) return VCV_EINVAL;
   hipLaunchKernelGGL(kl_bwd_kernel, g1(n), dim3(256), 0, ST, zp, mp, lp, mask, gout, den, dzp, dlq, dmp, dlp, C, T,
                      n);
   return vcv_check_launch();
@@ -980,14 +987,14 @@ extern "C" int vcv_kl_bwd(const float* zp, const float* mp, const float* lp, con
 
 extern "C" int vcv_nearest_fwd(const float* x, float* y, int R, int Tin, int Tout, void* stream) {
   const size_t n = (size_t)R * Tout;
-  if (!x || !y || n == 0 || Tin <= 0) return VCV_EINVAL;
+  if (!x || !y || !pos(R, Tin, Tout)) return VCV_EINVAL;
   hipLaunchKernelGGL(nearest_fwd_kernel, g1(n), dim3(256), 0, ST, x, y, Tin, Tout, n);
   return vcv_check_launch();
 }
 
 extern "C" int vcv_nearest_bwd(const float* dy, float* dx, int R, int Tin, int Tout, void* stream) {
   const size_t n = (size_t)R * Tout;
-  if (!dy || !dx || n == 0 || Tin <= 0) return VCV_EINVAL;
+  if (!dy || !dx || !pos(R, Tin, Tout)) return VCV_EINVAL;
   if (vcv_zero_async(dx, sizeof(float) * (size_t)R * Tin, ST) != hipSuccess) return VCV_EHIP;
   hipLaunchKernelGGL(nearest_bwd_kernel, g1(n), dim3(256), 0, ST, dy, dx, Tin, Tout, n);
   return vcv_check_launch();
@@ -995,14 +1002,14 @@ extern "C" int vcv_nearest_bwd(const float* dy, float* dx, int R, int Tin, int T
 
 extern "C" int vcv_nearest_raw_fwd(const float* x, float* y, int R, int Tin, int Tout, const void* raw, void* stream) {
   const size_t n = (size_t)R * Tout;
-  if (!x || !y || !raw || n == 0 || Tin <= 0) return VCV_EINVAL;
+  if (!x || !y || !raw || !pos(R, Tin, Tout)) return VCV_EINVAL;
   hipLaunchKernelGGL(nearest_raw_fwd_kernel, g1(n), dim3(256), 0, ST, x, y, Tin, Tout, (const long long*)raw, n);
   return vcv_check_launch();
 }
 
 extern "C" int vcv_nearest_raw_bwd(const float* dy, float* dx, int R, int Tin, int Tout, const void* raw, void* stream) {
   const size_t n = (size_t)R * Tout;
-  if (!dy || !dx || !raw || n == 0 || Tin <= 0) return VCV_EINVAL;
+  if (!dy || !dx || !raw || !pos(R, Tin, Tout)) return VCV_EINVAL;
   if (vcv_zero_async(dx, sizeof(float) * (size_t)R * Tin, ST) != hipSuccess) return VCV_EHIP;
   hipLaunchKernelGGL(nearest_raw_bwd_kernel, g1(n), dim3(256), 0, ST, dy, dx, Tin, Tout, (const long long*)raw, n);
   return vcv_check_launch();
@@ -1011,7 +1018,7 @@ extern "C" int vcv_nearest_raw_bwd(const float* dy, float* dx, int R, int Tin, i
 extern "C" int vcv_slice_fwd(const float* x, const int64_t* ids, int mul, float* y, int B, int C, int T, int S,
                              void* stream) {
   const size_t n = (size_t)B * C * S;
-  if (!x || !ids || !y || n == 0) return VCV_EINVAL;
+  if (!x || !ids || !y || !pos(B, C, T) || S <= 0) return VCV_EINVAL;
   hipLaunchKernelGGL(slice_fwd_kernel, g1(n), dim3(256), 0, ST, x, ids, mul, y, C, T, S, n);
   return vcv_check_launch();
 }
@@ -1019,7 +1026,7 @@ extern "C" int vcv_slice_fwd(const float* x, const int64_t* ids, int mul, float*
 extern "C" int vcv_slice_bwd(const float* dy, const int64_t* ids, int mul, float* dx, int B, int C, int T, int S,
                              void* stream) {
   const size_t n = (size_t)B * C * S;
-  if (!dy || !ids || !dx || n == 0) return VCV_EINVAL;
+  if (!dy || !ids || !dx || !pos(B, C, T) || S <= 0) return VCV_EINVAL;
   if (vcv_zero_async(dx, sizeof(float) * (size_t)B * C * T, ST) != hipSuccess) return VCV_EHIP;
   hipLaunchKernelGGL(slice_bwd_kernel, g1(n), dim3(256), 0, ST, dy, ids, mul, dx, C, T, S, n);
   return vcv_check_launch();
