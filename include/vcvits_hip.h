@@ -242,12 +242,20 @@ typedef struct VcvWgradArgs {
                          (summation order varies from run to run).  Non-NULL: each writes its partial tile to its own
                          slab of Mg*Cg*K floats and a finishing pass adds the slabs in a fixed order -- bit-reproducible */
   int64_t slab_floats; /* capacity of `slab`; the split is limited to slab_floats / (Mg*Cg*K) ways */
+  int32_t split_terms; /* arithmetic of vcv_conv_wgrad's MFMA kernel (wgrad_dma.hip): 0 = fp32-input MFMA; 6 = the fp32
+                          operands split into three exact bf16 terms each in registers and multiplied with six bf16 MFMA
+                          products (the arithmetic of vcv_conv_x3_*), where the library wants it -- nine-term mode, tuning key
+                          wgrad_dma_split = 0 and the shapes the fp32-input body is faster on keep 0.  Anything else is
+                          VCV_EINVAL.  The other entry points ignore the field. */
 } VcvWgradArgs;
 
 int vcv_conv_wgrad(const VcvWgradArgs* args, void* stream);
 /* 1: vcv_conv_wgrad runs this launch on the LDS-DMA weight-gradient kernel (wgrad_dma.hip); 0: on the register-staged one
  * (grouped launches, derivative-masked operands, rows under 64 positions, (C, K) blocks under 96 columns). */
 int vcv_conv_wgrad_takes_dma(const VcvWgradArgs* args);
+/* Product terms of the arithmetic vcv_conv_wgrad runs this launch in (host only): 6 = the split-operand form of the LDS-DMA
+ * kernel (args->split_terms == 6 and the library wants the shape), 0 = fp32 inputs. */
+int vcv_conv_wgrad_split_terms(const VcvWgradArgs* args);
 
 /*
  * bf16-operand weight gradient (same VcvWgradArgs, G == 1, transforms NONE / LEAKY): operands rounded to bf16 on their

@@ -368,6 +368,7 @@ extern "C" int vcv_conv_wgrad(const VcvWgradArgs* args, void* stream) {
     return VCV_EINVAL;
   if (a.a_tf >= VCV_TF_DLEAKY && !a.aaux) return VCV_EINVAL;
   if (a.b_tf >= VCV_TF_DLEAKY && !a.baux) return VCV_EINVAL;
+  if (a.split_terms != 0 && a.split_terms != 6) return VCV_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const int N = a.Cg * a.K;
   const bool use_dma = vcv_tuning().wgrad_dma != 0;

@@ -38,10 +38,10 @@
 #include "prof.h"
 #include "conv_tile.h"
 #include "conv_plan.h"
+#include "split_terms.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void* lds_ptr;
 
 // diagnostic build only (-DVCV_X3_STAMPS, tools/probes/x3_stamps.py): 100 MHz stamps of workgroup phases; the product build
@@ -61,41 +61,6 @@ constexpr int NPROD = 4;  // producer waves: 1 weight-DMA wave + 3 input-staging
 constexpr int NXW = 3;
 constexpr int MAXT = 2;   // pipelined staging tasks per input wave and stage
 constexpr int NRING_DEF = 4;  // weight-slab ring slots (a power of two; the 256-row tile takes 2)
-
-// one term a_PA * b_PB of the split product on every accumulator tile of the wave (literal plane indices: a computed
-// index makes the compiler select fragment registers at run time)
-template <int PA, int PB, int TM, int TN>
-__device__ __forceinline__ void mma_term(f32x16 (&acc)[TM][TN], const bf16x8 (&a)[TM][3], const bf16x8 (&b)[TN][3]) {
-#pragma unroll
-  for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn)
-      acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm][PA], b[tn][PB], acc[tm][tn], 0, 0, 0);
-}
-
-// the NTERM terms of one split product, small terms first
-template <int NTERM, int TM, int TN>
-__device__ __forceinline__ void mma_product(f32x16 (&acc)[TM][TN], const bf16x8 (&a)[TM][3], const bf16x8 (&b)[TN][3]) {
-  if (NTERM == 9) {
-    mma_term<2, 2>(acc, a, b);
-    mma_term<1, 2>(acc, a, b);
-    mma_term<2, 1>(acc, a, b);
-  }
-  mma_term<0, 2>(acc, a, b);
-  mma_term<2, 0>(acc, a, b);
-  mma_term<1, 1>(acc, a, b);
-  mma_term<0, 1>(acc, a, b);
-  mma_term<1, 0>(acc, a, b);
-  mma_term<0, 0>(acc, a, b);
-}
-
-__device__ __forceinline__ void split3(float f, __bf16& t0, __bf16& t1, __bf16& t2) {
-  t0 = (__bf16)f;
-  const float r1 = f - (float)t0;   // exact
-  t1 = (__bf16)r1;
-  const float r2 = r1 - (float)t1;  // exact, and representable in 8 bits
-  t2 = (__bf16)r2;
-}
 
 // ---- weight pack: fp32 w -> split bf16 slabs wp[phase][m-tile][group][j][term][h][m][8] -----------------------------
 // mode 0: w is [M, C, K] (forward);  mode 1: w is [C, M, K], A(m, c, j) = w[c, m, K-1-j] (stride-1 data gradient);

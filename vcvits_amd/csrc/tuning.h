@@ -27,6 +27,7 @@ struct VcvTuning {
   int wgrad_dma = 1;       // the LDS-DMA weight-gradient kernel (0: the register-staged one)
   int wgrad_tile = -1;     // wgrad_dma: fix the tile candidate (-1: the cost model)
   int wgrad_verbose = 0;   // wgrad_dma: print every plan
+  int wgrad_dma_split = 1;  // wgrad_dma: the six-term split-operand body where a launch offers it (0: fp32-input MFMA)
   int wgrad_bf16_ws = 1;   // producer waves in the bf16-operand weight gradient
   int wgrad_finish_vec = 1;  // 16-byte slab reads in the finishing pass
   int bias_rows = 1;       // one workgroup per channel for short rows in vcv_bias_grad

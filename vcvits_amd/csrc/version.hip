@@ -21,7 +21,7 @@ struct TuningKey { const char* name; int VcvTuning::*field; };
 #define TK(f) {#f, &VcvTuning::f}
 const TuningKey kTuningKeys[] = {
     TK(xcd_remap), TK(pk_ws), TK(pk_ws_bf16), TK(pk_x4), TK(pk_vec), TK(x3_variant), TK(x3_v6), TK(x3_js2), TK(x3_merge_phases), TK(x3_old_ks), TK(x3_all),
-    TK(x3_terms), TK(wgrad_dma), TK(wgrad_tile), TK(wgrad_verbose), TK(wgrad_bf16_ws), TK(wgrad_finish_vec), TK(bias_rows),
+    TK(x3_terms), TK(wgrad_dma), TK(wgrad_tile), TK(wgrad_verbose), TK(wgrad_dma_split), TK(wgrad_bf16_ws), TK(wgrad_finish_vec), TK(bias_rows),
     TK(c1_chunk), TK(m1_lds), TK(c1_wgrad_pairs), TK(thin_wgrad_wgs), TK(act_grad_vec), TK(ln_regs), TK(stft_wave), TK(attn_rows),
     TK(zero_memset), TK(pack_tile), TK(pack_tile_bf16), TK(pair_dbg), TK(pair_grid), TK(pair_stream), TK(deterministic)};
 #undef TK

@@ -25,8 +25,18 @@
 //   register-staged producers that de-interleave strided rows by residue as they write                104 / 65
 //       (~25 VALU instructions per element: one producer wave per SIMD cannot keep up)
 // One barrier per stage; input leaky-ReLU (ResBlock / generator convs) is applied to the fragments as read.
+//
+// Two arithmetics on the same LDS images (template parameter ST, VcvWgradArgs.split_terms):
+//   ST = 0   fp32-input MFMA as above: 8 x v_mfma_f32_32x32x2_f32 per 16 positions and tile pair (512 cycles per SIMD);
+//   ST = 6   split-operand: the fp32 fragments of 16 positions (eight floats per lane and row) are split in registers into
+//            their three exact bf16 terms (split_terms.h, the arithmetic of conv_x3.hip) and multiplied with 6 x
+//            v_mfma_f32_32x32x16_bf16 (192 cycles).  Staging, LDS footprint and HBM traffic are those of ST = 0, so every
+//            shape that fits there fits here.  A lane half holds 8 of the 16 reduction elements of such an MFMA; WHICH eight
+//            is free as long as both operands agree, so the half keeps the positions it reads today (4h..4h+3 and
+//            8+4h..8+4h+3 of the sixteen: the same two 16-byte reads per row at offsets 0 and 32 bytes).
 #include "common.h"
 #include "prof.h"
+#include "split_terms.h"
 #include <cstring>
 #include <unordered_map>
 
@@ -56,6 +66,7 @@ __device__ __forceinline__ float lds_rd32(unsigned addr) {
 __device__ __forceinline__ void lds_wait() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void pin(f32x4& f) { asm volatile("" : "+v"(f)); }
 __device__ __forceinline__ void pin(float& f) { asm volatile("" : "+v"(f)); }
+__device__ __forceinline__ void pin(bf16x8& f) { asm volatile("" : "+v"(f)); }
 template <typename T, int N>
 __device__ __forceinline__ void pin(T (&f)[N]) {
 #pragma unroll
@@ -72,7 +83,17 @@ __device__ __forceinline__ f32x4 ld128(__amdgpu_buffer_rsrc_t r, unsigned voff) 
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
 }
 
-template <int TM, int TN, int WM, int WN, bool LA, bool LB, bool BIAS, bool STR>
+// the three bf16 terms of the eight floats a lane holds of one fragment row (lo: positions 4h.., hi: positions 8+4h..)
+__device__ __forceinline__ void split_frag(const float (&f)[8], bf16x8 (&t)[3]) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    __bf16 t0, t1, t2;
+    split3(f[e], t0, t1, t2);
+    t[0][e] = t0, t[1][e] = t1, t[2][e] = t2;
+  }
+}
+
+template <int TM, int TN, int WM, int WN, bool LA, bool LB, bool BIAS, bool STR, int ST>
 __global__ void __launch_bounds__(64 * (WM * WN + (WM * WN >= 8 ? 4 : 2)))
 wgrad_dma_kernel(const VcvWgradArgs p, const WgGeom tg) {
   constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN, NW = WM * WN, NP = NW >= 8 ? 4 : 2;
@@ -245,6 +266,100 @@ wgrad_dma_kernel(const VcvWgradArgs p, const WgGeom tg) {
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn) bad[tn] = base + nofs[tn];
 
+
+    if constexpr (ST == 6) {
+      // ---- split-operand stage: per sixteen positions the eight floats of every fragment row are read (into the registers
+      // the previous group has just been split out of), transformed, summed for the bias and split into three bf16 planes;
+      // the reads of the next group are issued before the six MFMA terms of this one and arrive while they run
+      f32x4 a0[TM], a1[TM], b0[TN], b1[TN], t0, t1;
+      float b0s[TN][4], b1s[TN][4];
+      // strided: the eight table entries of the group are read first and waited for alone (LDS reads return in order:
+      // when at most the 2 * TM reads of the A rows are outstanding, the entries have arrived), then address the dword
+      // reads of the B side.  The entries are not read a group ahead as in the fp32 body: eight more live registers
+      // across the MFMAs put the 128x256 tile over its 168
+      auto rd_group = [&]() __attribute__((always_inline)) {
+        if (STR) t0 = lds_rd128<0>(tad), t1 = lds_rd128<32>(tad);
+#pragma unroll
+        for (int tm = 0; tm < TM; ++tm) a0[tm] = lds_rd128<0>(aad[tm]), a1[tm] = lds_rd128<32>(aad[tm]);
+        if (STR) {
+          asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(2 * TM) : "memory");
+          pin(t0), pin(t1);
+        }
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) {
+          if (!STR) {
+            b0[tn] = lds_rd128<0>(bad[tn]), b1[tn] = lds_rd128<32>(bad[tn]);
+          } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) b0s[tn][e] = lds_rd32(bad[tn] + __float_as_uint(t0[e]));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) b1s[tn][e] = lds_rd32(bad[tn] + __float_as_uint(t1[e]));
+          }
+        }
+      };
+      // the reads of a group are waited for and their registers redefined BEFORE the loop's back-edge, as in the fp32
+      // body: no value that is still in flight is carried around the loop, where a register copy could read it early
+      auto settle = [&]() __attribute__((always_inline)) {
+        lds_wait();
+        pin(a0), pin(a1);
+        if (STR) {
+#pragma unroll
+          for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pin(b0s[tn][e]), pin(b1s[tn][e]);
+        } else {
+          pin(b0), pin(b1);
+        }
+      };
+      rd_group();
+      settle();
+      for (int pr = 0; pr < npair; ++pr) {
+        bf16x8 ap[TM][3], bp[TN][3];
+#pragma unroll
+        for (int tm = 0; tm < TM; ++tm) {
+          float f[8];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) f[e] = a0[tm][e], f[4 + e] = a1[tm][e];
+          if (LA) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) f[e] = fmaxf(f[e], f[e] * p.slope);
+          }
+          if (BIAS && do_bias) bsum[tm] += ((f[0] + f[1]) + (f[2] + f[3])) + ((f[4] + f[5]) + (f[6] + f[7]));
+          split_frag(f, ap[tm]);
+        }
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) {
+          float f[8];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) f[e] = STR ? b0s[tn][e] : b0[tn][e], f[4 + e] = STR ? b1s[tn][e] : b1[tn][e];
+          if (LB) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) f[e] = fmaxf(f[e], f[e] * p.slope);
+          }
+          split_frag(f, bp[tn]);
+        }
+        // (the planes are complete before the fragment registers are read into again)
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl) {
+#pragma unroll
+          for (int tm = 0; tm < TM; ++tm) pin(ap[tm][pl]);
+#pragma unroll
+          for (int tn = 0; tn < TN; ++tn) pin(bp[tn][pl]);
+        }
+#pragma unroll
+        for (int tm = 0; tm < TM; ++tm) aad[tm] += 64;
+        if (!STR) {
+#pragma unroll
+          for (int tn = 0; tn < TN; ++tn) bad[tn] += 64;
+        }
+        tad += 64;
+        if (pr + 1 < npair) rd_group();
+        mma_product<6>(acc, ap, bp);
+        settle();  // (nothing outstanding after the stage's last group)
+      }
+      bufi ^= 1;
+      continue;
+    }
     // (strided: the dword reads land in scalar registers b0s / b1s -- an asm output that is then moved into a vector
     // element would be copied before its data has arrived)
     f32x4 a0[TM], a1[TM], b0[TN], b1[TN], t0, t1;
@@ -354,13 +469,44 @@ __global__ void __launch_bounds__(256) wgrad_slab_finish_kernel(const float* __r
   dw[i] += alpha * s;
 }
 
-template <int TM, int TN, int WM, int WN, bool STR>
-void (*pick_kernel(const VcvWgradArgs& a))(const VcvWgradArgs, const WgGeom) {
+template <int TM, int TN, int WM, int WN, bool STR, int ST>
+void (*pick_kernel_st(const VcvWgradArgs& a))(const VcvWgradArgs, const WgGeom) {
   const bool la = a.a_tf == VCV_TF_LEAKY, lb = a.b_tf == VCV_TF_LEAKY;
   // the bias-collecting variant exists for the transform-free `a` operand only (a Conv's dy)
-  return la ? (lb ? wgrad_dma_kernel<TM, TN, WM, WN, true, true, false, STR> : wgrad_dma_kernel<TM, TN, WM, WN, true, false, false, STR>)
-            : (a.dbias ? (lb ? wgrad_dma_kernel<TM, TN, WM, WN, false, true, true, STR> : wgrad_dma_kernel<TM, TN, WM, WN, false, false, true, STR>)
-                       : (lb ? wgrad_dma_kernel<TM, TN, WM, WN, false, true, false, STR> : wgrad_dma_kernel<TM, TN, WM, WN, false, false, false, STR>));
+  return la ? (lb ? wgrad_dma_kernel<TM, TN, WM, WN, true, true, false, STR, ST> : wgrad_dma_kernel<TM, TN, WM, WN, true, false, false, STR, ST>)
+            : (a.dbias ? (lb ? wgrad_dma_kernel<TM, TN, WM, WN, false, true, true, STR, ST> : wgrad_dma_kernel<TM, TN, WM, WN, false, false, true, STR, ST>)
+                       : (lb ? wgrad_dma_kernel<TM, TN, WM, WN, false, true, false, STR, ST> : wgrad_dma_kernel<TM, TN, WM, WN, false, false, false, STR, ST>));
+}
+// split: the six-term split-operand body (ST = 6) instead of the fp32-input one
+template <int TM, int TN, int WM, int WN, bool STR>
+void (*pick_kernel(const VcvWgradArgs& a, bool split))(const VcvWgradArgs, const WgGeom) {
+  return split ? pick_kernel_st<TM, TN, WM, WN, STR, 6>(a) : pick_kernel_st<TM, TN, WM, WN, STR, 0>(a);
+}
+
+// Full-load rate of the split form per tile shape, relative to its 128x256 tile, and that tile's rate as a fraction of the
+// fp32 MFMA peak the cost model prices in: wgrad_tile sweep with wgrad_dma_split = 1 on the DiscP conv4 weight gradient at
+// period 37 (profiles/wgrad_dma_split_ab.txt: 133.7 / 110.9 / 87.2 / 98.2 / 89.7 / 76.5 / 76.7 TFLOP/s).  The narrow tiles
+// fall off faster than in the fp32 body: their split work per MFMA is the same and their MFMA waves per SIMD fewer.
+// Order: 128x256, 128x128, 128x64, 64x256, 64x128, 64x64, 32x128
+constexpr double SPLIT_SHAPE[7] = {1.0, 0.83, 0.65, 0.73, 0.67, 0.57, 0.57};
+constexpr double SPLIT_BASE = 0.85;
+
+// Shapes the split form takes under the default setting.  The rule is a threshold extrapolated from the vocoder workload's
+// rows of the layer bench (profiles/wgrad_dma_split_ab.txt), not a table of measured shapes: every row of the period
+// discriminators and of the generator's ResBlocks and upsamplers that reaches this kernel is ahead of the fp32 body by more
+// than the spread of its repeated runs, or level with it; none is behind.  The launches with under 1024 reduction positions
+// in all (the generator's conv_pre and first upsampler: 16 stages, a time set by the prologue and the epilogue's adds)
+// are level and keep the fp32-input body.  Two more rows are level within 1 us (gen.ups2, gen.res c256 k3) and stay on the
+// split form, since no shape feature separates them from neighbours that are ahead; shapes of other workloads with 1024
+// positions or more (the full model's 1 x 1 convs among them) take it unmeasured.
+bool wanted_split(const VcvWgradArgs& a) { return (long long)a.B * a.Ta * a.P >= 1024; }
+
+// the arithmetic of a launch: the six-term split form where the caller offers it (split_terms = 6), six terms are in
+// effect (nine-term mode keeps the fp32-input body: both are exact-operand arithmetic), the A/B key is on and the shape
+// is wanted (vcv_conv_x3_set_all(1) admits every shape)
+bool takes_split(const VcvWgradArgs& a) {
+  const VcvTuning& t = vcv_tuning();
+  return a.split_terms == 6 && t.wgrad_dma_split != 0 && t.x3_terms == 6 && (t.x3_all != 0 || wanted_split(a));
 }
 
 struct WgPlan {
@@ -375,7 +521,7 @@ struct WgPlan {
 //   [slab mode: the slab written and read back at streaming rates].
 // The stage time prices the MFMAs at the rate the tile shape reaches in this kernel (LDS instructions per MFMA).
 template <int TM, int TN, int WM, int WN, bool STR>
-WgPlan plan(const VcvWgradArgs& a) {
+WgPlan plan(const VcvWgradArgs& a, bool split) {
   constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN, NP = WM * WN >= 8 ? 4 : 2, NT = 64 * (WM * WN + NP);
   WgPlan pl;
   pl.cost = -1.0;
@@ -416,11 +562,11 @@ WgPlan plan(const VcvWgradArgs& a) {
   g.nchunk_u = (int)((U + BU - 1) / BU);
   const long long total = (long long)a.B * g.nchunk_u;
   // workgroups a CU holds (registers and LDS): asked once per kernel variant
-  void (*kern)(const VcvWgradArgs, const WgGeom) = pick_kernel<TM, TN, WM, WN, STR>(a);
-  static int occ_cache[2][2][2] = {};
-  int& oc = occ_cache[a.a_tf == VCV_TF_LEAKY][a.b_tf == VCV_TF_LEAKY][a.dbias != nullptr];
+  void (*kern)(const VcvWgradArgs, const WgGeom) = pick_kernel<TM, TN, WM, WN, STR>(a, split);
+  static int occ_cache[2][2][2][2] = {};
+  int& oc = occ_cache[split][a.a_tf == VCV_TF_LEAKY][a.b_tf == VCV_TF_LEAKY][a.dbias != nullptr];
   if (oc == 0) {
-    hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, VCV_LDS_LIMIT);
+    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, VCV_LDS_LIMIT);
     int nb = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kern, NT, 0) != hipSuccess || nb < 1) nb = 1;
     oc = nb;
@@ -433,7 +579,11 @@ WgPlan plan(const VcvWgradArgs& a) {
   const double shape = BM == 128 ? (BN == 256 ? 1.0 : BN == 128 ? 0.93 : 0.77)
                      : BM == 64  ? (BN == 256 ? 0.905 : BN == 128 ? 0.76 : 0.58)
                                  : 0.62;
-  const double rate = 0.70 * shape * (STR ? 0.93 : 1.0) * 157.3e12 / 256.0;  // per CU
+  // split form: the same table measured with wgrad_dma_split = 1 (SPLIT_SHAPE / SPLIT_BASE below)
+  const double shape6 = BM == 128 ? (BN == 256 ? SPLIT_SHAPE[0] : BN == 128 ? SPLIT_SHAPE[1] : SPLIT_SHAPE[2])
+                      : BM == 64  ? (BN == 256 ? SPLIT_SHAPE[3] : BN == 128 ? SPLIT_SHAPE[4] : SPLIT_SHAPE[5])
+                                  : SPLIT_SHAPE[6];
+  const double rate = (split ? SPLIT_BASE * shape6 : 0.70 * shape) * (STR ? 0.93 : 1.0) * 157.3e12 / 256.0;  // per CU
   const double t_stage = 2.0 * BM * BN * BU / rate * 1e6, t_fix = 4.0;
   const long long tiles = (long long)g.nnt * g.nmt;
   const long long slots = 256 * occ;
@@ -455,26 +605,28 @@ WgPlan plan(const VcvWgradArgs& a) {
   pl.cost = best;
   const bool verbose = vcv_tuning().wgrad_verbose != 0;
   if (verbose)
-    fprintf(stderr, "wgrad plan M%d C%d K%d U%lld s%d tile %dx%d: occ %lld tiles %lld total %lld Z %lld cost %.1f us lds %zu\n", a.Mg, a.Cg, a.K,
-            U, a.s, BM, BN, occ, tiles, total, Z, best, pl.lds);
+    fprintf(stderr, "wgrad plan M%d C%d K%d U%lld s%d tile %dx%d: occ %lld tiles %lld total %lld Z %lld cost %.1f us lds %zu%s\n", a.Mg, a.Cg, a.K,
+            U, a.s, BM, BN, occ, tiles, total, Z, best, pl.lds, split ? " terms 6" : "");
   return pl;
 }
 
 template <int TM, int TN, int WM, int WN, bool STR>
-int run(const VcvWgradArgs& a, const WgPlan& pl, hipStream_t st) {
+int run(const VcvWgradArgs& a, const WgPlan& pl, bool split, hipStream_t st) {
   constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN, NP = WM * WN >= 8 ? 4 : 2, NT = 64 * (WM * WN + NP);
   const WgGeom& g = pl.g;
-  void (*kern)(const VcvWgradArgs, const WgGeom) = pick_kernel<TM, TN, WM, WN, STR>(a);
+  void (*kern)(const VcvWgradArgs, const WgGeom) = pick_kernel<TM, TN, WM, WN, STR>(a, split);
   if (pl.lds > 64 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds) != hipSuccess)
     return VCV_EHIP;
   const int N = a.Cg * a.K;
   const size_t nw = (size_t)a.Mg * N;
   dim3 grid(g.nnt, g.nmt, g.Z), block(NT);
   const double flops = 2.0 * a.B * a.Mg * a.Cg * a.K * a.P * (double)a.Ta;
-  const int tag[12] = {a.B, 1, a.Cg, a.Mg, a.K, a.Ta, a.P, a.s, g.Z, 2, BM * 1000 + BN, g.G4};
+  // tag[1]: 1 = fp32-input MFMA, 4 = the six-term split form (2 / 3 are wgrad_bf16.hip's bf16 and three-plane launches)
+  const int tag[12] = {a.B, split ? 4 : 1, a.Cg, a.Mg, a.K, a.Ta, a.P, a.s, g.Z, 2, BM * 1000 + BN, g.G4};
   hipEvent_t ev0, ev1;
   const double abytes = 4.0 * ((double)a.B * a.Mg * a.Ta * a.P + (double)a.B * a.Cg * a.Tb * a.P + (double)a.Mg * a.Cg * a.K);
-  vcv_prof_events(VCV_PROF_WGRAD_DMA, flops, tag, 12, &ev0, &ev1, abytes);
+  if (split) vcv_prof_events(VCV_PROF_WGRAD_DMA, flops, tag, 12, &ev0, &ev1, abytes, 6 * flops / VCV_PEAK_BF16_MFMA);
+  else vcv_prof_events(VCV_PROF_WGRAD_DMA, flops, tag, 12, &ev0, &ev1, abytes);
   VCV_LAUNCH_EV(kern, grid, block, (unsigned)pl.lds, st, ev0, ev1, a, g);
   if (a.slab)
     hipLaunchKernelGGL(wgrad_slab_finish_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, st, (const float*)a.slab, a.dw,
@@ -488,14 +640,14 @@ int run(const VcvWgradArgs& a, const WgPlan& pl, hipStream_t st) {
 // plans are memoised per launch shape: evaluating seven tile shapes x up to 1024 splits costs ~50 us of host time,
 // which a launch-bound step (the 48 kHz full model) would pay two hundred times
 struct PlanKey {
-  int v[14];
+  int v[16];
   int64_t slab;
   bool operator==(const PlanKey& o) const { return memcmp(v, o.v, sizeof(v)) == 0 && slab == o.slab; }
 };
 struct PlanKeyHash {
   size_t operator()(const PlanKey& k) const {
     uint64_t h = 1469598103934665603ull ^ (uint64_t)k.slab;
-    for (int i = 0; i < 14; ++i) h = (h ^ (uint64_t)(uint32_t)k.v[i]) * 1099511628211ull;
+    for (int i = 0; i < 16; ++i) h = (h ^ (uint64_t)(uint32_t)k.v[i]) * 1099511628211ull;
     return (size_t)h;
   }
 };
@@ -503,9 +655,12 @@ struct PlanEntry { WgPlan pl; int which; };
 
 template <bool STR>
 int launch(const VcvWgradArgs& a, hipStream_t st) {
-  const int only = vcv_tuning().wgrad_tile;  // tuning sweeps (the plan cache below is keyed on the shape only: set it before the first launch)
+  const int only = vcv_tuning().wgrad_tile;  // tuning sweeps
+  const bool split = takes_split(a);
   static thread_local std::unordered_map<PlanKey, PlanEntry, PlanKeyHash> cache;
-  const PlanKey key = {{a.B, a.Cg, a.Mg, a.Ta, a.Tb, a.P, a.K, a.s, a.dj, a.off, a.a_tf, a.b_tf, a.dbias != nullptr, a.slab != nullptr},
+  // (the arithmetic and the forced tile are part of the key: both change the plan of a shape)
+  const PlanKey key = {{a.B, a.Cg, a.Mg, a.Ta, a.Tb, a.P, a.K, a.s, a.dj, a.off, a.a_tf, a.b_tf, a.dbias != nullptr, a.slab != nullptr,
+                        split, only},
                        a.slab ? a.slab_floats : 0};
   auto hit = cache.find(key);
   WgPlan best;
@@ -515,7 +670,7 @@ int launch(const VcvWgradArgs& a, hipStream_t st) {
   else {
 #define WG_PLAN(I, TM, TN, WM, WN)                                                        \
   if ((only < 0 || only == I) && a.Mg >= 32 * TM * WM / 2 + 1 || (I == 6 && which < 0)) { \
-    const WgPlan pl = plan<TM, TN, WM, WN, STR>(a);                                       \
+    const WgPlan pl = plan<TM, TN, WM, WN, STR>(a, split);                                \
     if (pl.cost >= 0.0 && (which < 0 || pl.cost < best.cost)) best = pl, which = I;       \
   }
   WG_TILES(WG_PLAN)
@@ -525,7 +680,7 @@ int launch(const VcvWgradArgs& a, hipStream_t st) {
   }
   if (which < 0) return -100;
 #define WG_RUN(I, TM, TN, WM, WN) \
-  if (which == I) return run<TM, TN, WM, WN, STR>(a, best, st);
+  if (which == I) return run<TM, TN, WM, WN, STR>(a, best, split, st);
   WG_TILES(WG_RUN)
 #undef WG_RUN
   return -100;
@@ -554,4 +709,10 @@ int vcv_wgrad_dma_try(const VcvWgradArgs& a, hipStream_t st) {
 // conv_wgrad_kernel (tools/fallback_census.py lists those shapes)
 extern "C" int vcv_conv_wgrad_takes_dma(const VcvWgradArgs* a) {
   return a && vcv_tuning().wgrad_dma != 0 && wgrad_dma_eligible(*a) ? 1 : 0;
+}
+
+// product terms of the arithmetic vcv_conv_wgrad runs this launch in: 6 = wgrad_dma_kernel's split-operand form, 0 = fp32
+// inputs (the fp32-input body of wgrad_dma_kernel, or the register-staged kernel)
+extern "C" int vcv_conv_wgrad_split_terms(const VcvWgradArgs* a) {
+  return vcv_conv_wgrad_takes_dma(a) && takes_split(*a) ? 6 : 0;
 }

@@ -49,6 +49,10 @@ def _launch_conv(a, flip_w=None, wt=None):
 
 
 def _launch_wgrad(a):
+    # vcv_conv_wgrad's MFMA kernel in the split-operand arithmetic too, under the condition that offers the launch to
+    # vcv_wgrad_x3 (which keeps first refusal); the library decides per shape
+    split = _COMPUTE[0] != "bf16" and _USE_X3[0] and _USE_X3_WGRAD[0] and lib().vcv_conv_x3_get_terms() == 6
+    a.split_terms = 6 if split else 0
     if _DETERMINISTIC[0] and a.G == 1:
         nw = a.Mg * a.Cg * a.K
         n = min(nw * 512, max(nw * 4, 24 << 20))

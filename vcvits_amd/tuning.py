@@ -49,7 +49,7 @@ def live_flag(name):
 
 # ---- the kernel-side table (csrc/tuning.h) ---------------------------------------------------------------------------------
 KERNEL_KEYS = ("xcd_remap", "pk_ws", "pk_ws_bf16", "pk_x4", "pk_vec", "x3_variant", "x3_v6", "x3_js2", "x3_merge_phases", "x3_old_ks", "x3_all", "x3_terms",
-               "wgrad_dma", "wgrad_tile", "wgrad_verbose", "wgrad_bf16_ws", "wgrad_finish_vec", "bias_rows", "c1_chunk", "m1_lds",
+               "wgrad_dma", "wgrad_tile", "wgrad_verbose", "wgrad_dma_split", "wgrad_bf16_ws", "wgrad_finish_vec", "bias_rows", "c1_chunk", "m1_lds",
                "c1_wgrad_pairs", "thin_wgrad_wgs", "act_grad_vec", "ln_regs", "stft_wave", "attn_rows", "zero_memset", "pack_tile",
                "pack_tile_bf16", "pair_dbg", "pair_grid", "pair_stream", "deterministic")
 
