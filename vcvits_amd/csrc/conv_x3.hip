@@ -17,21 +17,19 @@
 // bits -- by default, torch.backends.cudnn.allow_tf32; this keeps all 24.)
 //
 // Pipeline (one workgroup = NW MFMA waves + 4 producer waves, one output tile of BM channels x BN positions):
-//   * reduction step ("stage") = one 16-channel group x one tap.  Weights are split and packed ahead of time in HBM in
-//     LDS image order wp[phase][m-tile][group][tap][term][h][m][8 ch] (bf16): a stage's slab is contiguous and is
-//     copied by ONE producer wave with global_load_lds, 1 KiB per instruction, into a two-slot ring.
+//   * reduction step ("stage") = one 16-channel group x the taps of one weight-ring slot.  Weights are pre-split and packed in
+//     HBM in LDS image order wp[phase][m-tile][group][tap][term][h][m][8 ch] (bf16): ONE producer wave copies a tap's slab with
+//     global_load_lds, 1 KiB per instruction, into a ring up to three stages ahead: 4 slots of one or two taps (2 for the
+//     256-row tile), or 2 .. 4 slots of PH taps in the merged-phase form.
 //   * the input span of a channel group (all taps read the same span at shifted offsets) is staged by the other three
-//     producer waves: 16-byte buffer loads of four consecutive positions x 8 channels per lane (range-checked
-//     descriptors: zero padding, ragged tails and channel tails need no predicates), input leaky-ReLU, split into three
-//     bf16 terms, three 16-byte LDS writes per position; the loads of the task a wave converts in stage s + 1 are in
-//     flight during stage s (the producers pass the stage barrier with `s_waitcnt lgkmcnt(0)` only).  Two span buffers:
-//     group g + 1 is staged piecewise during the K stages of group g.
-//   * MFMA waves: per stage TM x 3 + TN x 3 `ds_read_b128` fragment reads feed TM x TN x NTERM MFMAs, interleaved over
-//     the wave's accumulator tiles so that consecutive MFMAs are independent.
-//   * phased launches (strided data gradients, transposed-conv forwards) of 2 or 3 output residues take the merged-phase
-//     form conv_x3_merged_kernel: one workgroup per (column tile, m-tile) for ALL residues -- the span is staged once, not
-//     once per residue, and the span fragments of a tap feed the weight slabs of every residue that has the tap (tuning key
-//     x3_merge_phases; more residues, and launches too small to fill the chip, stay one workgroup per residue).
+//     producer waves: 16-byte buffer loads of four consecutive positions x 8 channels per lane (range-checked descriptors:
+//     zero padding, ragged tails and channel tails need no predicates), input leaky-ReLU, split into three bf16 terms, three
+//     16-byte LDS writes per position; the loads of the task a wave converts in stage s + 1 are in flight during stage s (the
+//     producers pass the barrier with `s_waitcnt lgkmcnt(0)` only).  Two span buffers: group g + 1 is staged during group g.
+//   * MFMA waves: per tap TM x 3 + TN x 3 `ds_read_b128` fragment reads feed TM x TN x NTERM MFMAs, interleaved over
+//     the wave's accumulator tiles so that consecutive MFMAs are independent; one barrier per stage.
+//   * phased launches (strided data gradients, transposed-conv forwards) of 2 or 3 output residues take conv_x3_merged_kernel,
+//     one workgroup for ALL residues (x3_merge_phases; more residues, and launches too small to fill the chip, do not).
 #include <type_traits>
 
 #include "common.h"
@@ -60,7 +58,7 @@ __device__ unsigned long long* g_x3_stamps;
 constexpr int NPROD = 4;  // producer waves: 1 weight-DMA wave + 3 input-staging waves
 constexpr int NXW = 3;
 constexpr int MAXT = 2;   // pipelined staging tasks per input wave and stage
-constexpr int NRING_DEF = 4;  // weight-slab ring slots (a power of two; the 256-row tile takes 2)
+constexpr int NRING_DEF = 4;  // weight-slab ring slots (a power of two: conv_x3_kernel masks the slot index; the 256-row tile takes 2)
 
 // ---- weight pack: fp32 w -> split bf16 slabs wp[phase][m-tile][group][j][term][h][m][8] -----------------------------
 // mode 0: w is [M, C, K] (forward);  mode 1: w is [C, M, K], A(m, c, j) = w[c, m, K-1-j] (stride-1 data gradient);
@@ -561,23 +559,35 @@ bool make_plan_merged(const VcvConvArgs& a, int BM, int BN, int variant, Plan& p
   return true;
 }
 
-// variants: 0: 128x256 (8 MFMA waves of 2x2 tiles)   1: 128x128 (8 waves of 2x1)   2: 256x128 (8 waves of 2x2)   3: 64x256 (8 waves of 1x2)
-//           4: 64x128 (8 waves of 1x1)   5: 32x256 (8 waves of 1x1)   6: 64x512 (8 waves of 1x4)
-#define g_force_variant (vcv_tuning().x3_variant)  // tuning probe: -1 = choose
-#define g_all (vcv_tuning().x3_all)
-#define g_terms (vcv_tuning().x3_terms)
+// The tile variants (8 MFMA waves each): X(variant, TM, TN, WM, WN, ring slots, two-tap stages exist, merged form exists) gives
+// the forced geometry, every plan's tile, the merged mapping and the dispatch; run_n instantiates the kernels in row order.
+#define X3_VARIANTS(X)                              \
+  X(0, 2, 2, 2, 4, NRING_DEF, 1, 0) /* 128 x 256 */ \
+  X(1, 2, 1, 2, 4, NRING_DEF, 1, 1) /* 128 x 128 */ \
+  X(2, 2, 2, 4, 2, 2, 0, 0)         /* 256 x 128 */ \
+  X(3, 1, 2, 2, 4, NRING_DEF, 0, 1) /*  64 x 256 */ \
+  X(4, 1, 1, 2, 4, NRING_DEF, 0, 0) /*  64 x 128 */ \
+  X(6, 1, 4, 2, 4, NRING_DEF, 0, 0) /*  64 x 512 */ \
+  X(5, 1, 1, 1, 8, NRING_DEF, 0, 1) /*  32 x 256 */
+struct Variant { int BM, BN, NW, nring, js2, merged; };
+#define X3_ROW(V, TM, TN, WM, WN, NRING, JS2, MRG) v == V ? Variant{32 * TM * WM, 32 * TN * WN, WM * WN, NRING, JS2, MRG} :
+constexpr Variant variant(int v) { return X3_VARIANTS(X3_ROW) Variant{}; }  // (BM = 0: no such variant)
+#undef X3_ROW
+
+bool plan_variant(const VcvConvArgs& a, int v, Plan& pl, int js = 1) {
+  pl.variant = v;
+  return make_plan(a, variant(v).BM, variant(v).BN, variant(v).NW, pl, variant(v).nring, js);
+}
 int g_force_js = -1, g_force_ks = -1;
 
 bool choose(const VcvConvArgs& a, Plan& pl) {
   const int U = a.Q * a.P;
   if (U < 96) return false;
-  if (g_force_variant >= 0) {  // tools/x3_variant_sweep.py: one fixed tile shape for every launch that can take it
-    static const int VBM[7] = {128, 128, 256, 64, 64, 32, 64}, VBN[7] = {256, 128, 128, 256, 128, 256, 512};
-    const int v = g_force_variant;
-    if (v > 6 || a.Mg < (v == 5 ? 32 : VBM[v] / 2 + 1)) return false;
-    const int js = (g_force_js == 2 && (v == 0 || v == 1) && vcv_cdiv(a.K, conv_phases(a)) >= 2) ? 2 : 1;
-    if (!make_plan(a, VBM[v], VBN[v], 8, pl, v == 2 ? 2 : NRING_DEF, js)) return false;
-    pl.variant = v;
+  // tools/x3_variant_sweep.py: one fixed tile shape for every launch that can take it
+  if (const int v = vcv_tuning().x3_variant; v >= 0) {
+    if (!variant(v).BM || a.Mg < (variant(v).BM == 32 ? 32 : variant(v).BM / 2 + 1)) return false;
+    const int js = (g_force_js == 2 && variant(v).js2 && vcv_cdiv(a.K, conv_phases(a)) >= 2) ? 2 : 1;
+    if (!plan_variant(a, v, pl, js)) return false;
     if (g_force_ks >= 2 && conv_phases(a) == 1 && pl.g.nch >= 2 * g_force_ks) {
       pl.g.ks = g_force_ks;
       pl.scratch_floats = (size_t)g_force_ks * a.B * a.Mg * U;
@@ -592,39 +602,38 @@ bool choose(const VcvConvArgs& a, Plan& pl) {
   // with workgroups that run all K taps per group instead of ceil(K / phases): where even the per-residue grid is no more
   // than one round of 256 workgroups, that form finishes sooner (every tap in parallel) and keeps the launch.
   if (vcv_tuning().x3_merge_phases && (nph == 2 || nph == 3)) {
-    const int bm = a.Mg >= 96 ? 128 : a.Mg >= 48 ? 64 : 32, bn = a.Mg >= 96 ? 128 : 256;
-    const long long nbm = (long long)a.B * vcv_cdiv(U, bn) * vcv_cdiv(a.Mg, bm);
-    if ((g_all || nbm * nph > 256) && make_plan_merged(a, bm, bn, bm == 128 ? 1 : bm == 64 ? 3 : 5, pl)) return true;
+    const int v = a.Mg >= 96 ? 1 : a.Mg >= 48 ? 3 : 5;  // 128 x 128, 64 x 256, 32 x 256
+    const long long nbm = (long long)a.B * vcv_cdiv(U, variant(v).BN) * vcv_cdiv(a.Mg, variant(v).BM);
+    if ((vcv_tuning().x3_all || nbm * nph > 256) && make_plan_merged(a, variant(v).BM, variant(v).BN, v, pl)) return true;
   }
   auto blocks = [&](int bm, int bn) { return conv_blocks(a, bm, bn); };
   auto eff = [&](int bm, int bn) { return conv_round_fill_rows(a, bm, bn); };
   bool ok = false;
   if (a.Mg >= 96) {
     const double e256 = U > 160 ? eff(128, 256) : 0.0, e128 = eff(128, 128);
-    if (e256 >= e128 - 0.02 && e256 > 0.0 && make_plan(a, 128, 256, 8, pl)) pl.variant = 0, ok = true;
+    if (e256 >= e128 - 0.02 && e256 > 0.0 && plan_variant(a, 0, pl)) ok = true;
     // 128 columns (the strided layers, whose input span is stride x as long, do not fit 256): 256 rows x 128 columns keeps
     // the 2 x 2 accumulator tiles per wave (12 fragment reads per 24 MFMAs instead of 9 per 12) with a two-slot ring
-    else if (a.Mg >= 256 && eff(256, 128) >= e128 - 0.1 && make_plan(a, 256, 128, 8, pl, 2)) pl.variant = 2, ok = true;
-    else if (make_plan(a, 128, 128, 8, pl)) pl.variant = 1, ok = true;
+    else if (a.Mg >= 256 && eff(256, 128) >= e128 - 0.1 && plan_variant(a, 2, pl)) ok = true;
+    else if (plan_variant(a, 1, pl)) ok = true;
   } else if (a.Mg >= 48) {
     // 64 x 512 (8 waves of 1 x 4 tiles: 15 fragment reads per 24 MFMAs instead of 9 per 12) where 64 x 256 needs more than one
     // round of 256 workgroups and the wider tile still fills the chip: the generator's 64-channel layers ran two full
     // rounds, each with its own 4 us prologue and 6 us store burst (tools/probes/x3_stamps.py)
     const bool no_v6 = !vcv_tuning().x3_v6;
     if (!no_v6 && nph == 1 && blocks(64, 256) > 256 && blocks(64, 512) >= 192 && eff(64, 512) >= eff(64, 256) - 0.02 &&
-        make_plan(a, 64, 512, 8, pl))
-      pl.variant = 6, ok = true;
-    else if (U > 160 && eff(64, 256) >= eff(64, 128) - 0.02 && make_plan(a, 64, 256, 8, pl)) pl.variant = 3, ok = true;
-    else if (make_plan(a, 64, 128, 8, pl)) pl.variant = 4, ok = true;
+        plan_variant(a, 6, pl)) ok = true;
+    else if (U > 160 && eff(64, 256) >= eff(64, 128) - 0.02 && plan_variant(a, 3, pl)) ok = true;
+    else if (plan_variant(a, 4, pl)) ok = true;
   } else {
-    if (make_plan(a, 32, 256, 8, pl)) pl.variant = 5, ok = true;
+    if (plan_variant(a, 5, pl)) ok = true;
   }
   if (!ok) return false;
   // two taps per stage where the doubled weight ring fits (128-row tiles, K >= 2): half the barriers per MFMA
   const bool no_js2 = !vcv_tuning().x3_js2;
-  if (!no_js2 && (pl.variant == 0 || pl.variant == 1) && vcv_cdiv(a.K, nph) >= 2) {
+  if (!no_js2 && variant(pl.variant).js2 && vcv_cdiv(a.K, nph) >= 2) {
     Plan p2;
-    if (make_plan(a, pl.BM, pl.BN, pl.NW, p2, NRING_DEF, 2)) { p2.variant = pl.variant; pl = p2; }
+    if (plan_variant(a, pl.variant, p2, 2)) pl = p2;
   }
   // too few tiles for 256 CUs: split the channel groups over ks workgroups per tile (deterministic slabs + finishing pass)
   const long long nb = blocks(pl.BM, pl.BN);
@@ -673,43 +682,33 @@ int pack_and_launch(Kern kern, const VcvConvArgs& a, const Plan& pl, char* wp, L
                           conv_pk_finish_kernel, conv_pk_finish4_kernel, g.vec != 0);
 }
 
-template <int NTERM, int TM, int TN, int WM, int WN, int NRING = NRING_DEF, int JS = 1>
+template <int NTERM, int PH, int TM, int TN, int WM, int WN, int NRING, int JS>  // PH = 0: conv_x3_kernel;  2, 3: the merged form
 int launch(const VcvConvArgs& a, const Plan& pl, char* wp, float* part, int flip, bool pack_valid, hipStream_t st, int32_t* desc) {
-  void (*kern)(const VcvConvArgs, const BfGeom, const char*, float*) =
-      a.in_tf == VCV_TF_LEAKY ? conv_x3_kernel<NTERM, TM, TN, WM, WN, true, NRING, JS> : conv_x3_kernel<NTERM, TM, TN, WM, WN, false, NRING, JS>;
-  return pack_and_launch<NTERM, 32 * TM * WM, 64 * (WM * WN + NPROD)>(kern, a, pl, wp, part, flip, pack_valid, st, desc);
-}
-
-template <int NTERM, int PH, int TM, int TN, int WM, int WN>
-int launch_merged(const VcvConvArgs& a, const Plan& pl, char* wp, int flip, bool pack_valid, hipStream_t st, int32_t* desc) {
-  void (*kern)(const VcvConvArgs, const BfGeom, const char*, int) =
-      a.in_tf == VCV_TF_LEAKY ? conv_x3_merged_kernel<NTERM, PH, TM, TN, WM, WN, true> : conv_x3_merged_kernel<NTERM, PH, TM, TN, WM, WN, false>;
-  return pack_and_launch<NTERM, 32 * TM * WM, 64 * (WM * WN + NPROD)>(kern, a, pl, wp, pl.nring, flip, pack_valid, st, desc);
-}
-
-template <int NTERM, int PH>
-int run_merged(const VcvConvArgs& a, const Plan& pl, char* wp, int flip, bool pv, hipStream_t st, int32_t* desc) {
-  switch (pl.variant) {
-    case 1: return launch_merged<NTERM, PH, 2, 1, 2, 4>(a, pl, wp, flip, pv, st, desc);  // 128 x 128
-    case 3: return launch_merged<NTERM, PH, 1, 2, 2, 4>(a, pl, wp, flip, pv, st, desc);  // 64 x 256
-    default: return launch_merged<NTERM, PH, 1, 1, 1, 8>(a, pl, wp, flip, pv, st, desc);  // 32 x 256
-  }
+  constexpr int BM = 32 * TM * WM, NT = 64 * (WM * WN + NPROD);
+  const bool leaky = a.in_tf == VCV_TF_LEAKY;
+  if constexpr (PH > 0)
+    return pack_and_launch<NTERM, BM, NT>(leaky ? conv_x3_merged_kernel<NTERM, PH, TM, TN, WM, WN, true> : conv_x3_merged_kernel<NTERM, PH, TM, TN, WM, WN, false>,
+                                          a, pl, wp, pl.nring, flip, pack_valid, st, desc);
+  else
+    return pack_and_launch<NTERM, BM, NT>(leaky ? conv_x3_kernel<NTERM, TM, TN, WM, WN, true, NRING, JS> : conv_x3_kernel<NTERM, TM, TN, WM, WN, false, NRING, JS>,
+                                          a, pl, wp, part, flip, pack_valid, st, desc);
 }
 
 template <int NTERM>
 int run_n(const VcvConvArgs& a, const Plan& pl, char* wp, float* part, int flip, bool pv, hipStream_t st, int32_t* desc) {
-  if (pl.merged) return pl.g.phases == 2 ? run_merged<NTERM, 2>(a, pl, wp, flip, pv, st, desc) : run_merged<NTERM, 3>(a, pl, wp, flip, pv, st, desc);
-  switch (pl.variant) {
-    case 0: return pl.js == 2 ? launch<NTERM, 2, 2, 2, 4, NRING_DEF, 2>(a, pl, wp, part, flip, pv, st, desc)
-                              : launch<NTERM, 2, 2, 2, 4>(a, pl, wp, part, flip, pv, st, desc);
-    case 1: return pl.js == 2 ? launch<NTERM, 2, 1, 2, 4, NRING_DEF, 2>(a, pl, wp, part, flip, pv, st, desc)
-                              : launch<NTERM, 2, 1, 2, 4>(a, pl, wp, part, flip, pv, st, desc);
-    case 2: return launch<NTERM, 2, 2, 4, 2, 2>(a, pl, wp, part, flip, pv, st, desc);  // 256 x 128
-    case 3: return launch<NTERM, 1, 2, 2, 4>(a, pl, wp, part, flip, pv, st, desc);
-    case 4: return launch<NTERM, 1, 1, 2, 4>(a, pl, wp, part, flip, pv, st, desc);
-    case 6: return launch<NTERM, 1, 4, 2, 4>(a, pl, wp, part, flip, pv, st, desc);  // 64 x 512
-    default: return launch<NTERM, 1, 1, 1, 8>(a, pl, wp, part, flip, pv, st, desc);
+  auto pass = [&](auto ph) {  // one pass over the table per form: PH = 2, PH = 3, then per residue (PH = 0)
+    constexpr int PH = decltype(ph)::value;
+#define X3_RUN(V, TM, TN, WM, WN, NRING, JS2, MRG)                                                                             \
+  if constexpr (PH == 0 || MRG) if (pl.variant == V) {                                                                         \
+    if constexpr (PH == 0 && JS2) if (pl.js == 2) return launch<NTERM, 0, TM, TN, WM, WN, NRING, 2>(a, pl, wp, part, flip, pv, st, desc); \
+    return launch<NTERM, PH, TM, TN, WM, WN, NRING, 1>(a, pl, wp, part, flip, pv, st, desc);                                   \
   }
+    X3_VARIANTS(X3_RUN)
+#undef X3_RUN
+    return (int)VCV_EINVAL;  // (also: a merged plan on a tile without a merged form)
+  };
+  if (pl.merged) return pl.g.phases == 2 ? pass(std::integral_constant<int, 2>()) : pass(std::integral_constant<int, 3>());
+  return pass(std::integral_constant<int, 0>());
 }
 
 }  // namespace
@@ -717,20 +716,20 @@ int run_n(const VcvConvArgs& a, const Plan& pl, char* wp, float* part, int flip,
 // Number of bf16 product terms per fp32 product: 9 (all of them: exact operands) or 6 (the three smallest left out).
 extern "C" int vcv_conv_x3_set_terms(int n) {
   if (n != 6 && n != 9) return VCV_EINVAL;
-  g_terms = n;
+  vcv_tuning().x3_terms = n;
   return VCV_OK;
 }
-extern "C" int vcv_conv_x3_get_terms(void) { return g_terms; }
+extern "C" int vcv_conv_x3_get_terms(void) { return vcv_tuning().x3_terms; }
 // all != 0: take every eligible launch (tests); 0: only the shapes where this kernel is the faster one (wanted())
 extern "C" int vcv_conv_x3_set_all(int all) {
-  g_all = all ? 1 : 0;
+  vcv_tuning().x3_all = all ? 1 : 0;
   return VCV_OK;
 }
-extern "C" int vcv_conv_x3_get_all(void) { return g_all; }
+extern "C" int vcv_conv_x3_get_all(void) { return vcv_tuning().x3_all; }
 // Tuning probe (tools/x3_variant_sweep.py): fix the tile variant (0..6: 128x256, 128x128, 256x128, 64x256, 64x128, 32x256,
 // 64x512; -1 = the library's choice), the taps per stage (2 or 1) and the channel-group split (>= 2, or -1) of every launch.
 extern "C" int vcv_conv_x3_set_variant(int variant, int js, int ks) {
-  g_force_variant = variant;
+  vcv_tuning().x3_variant = variant;
   g_force_js = js;
   g_force_ks = ks;
   return VCV_OK;
@@ -742,7 +741,7 @@ extern "C" int vcv_conv_x3_set_variant(int variant, int js, int ks) {
 // (tools/prof_compare.py on the bench workload): everything but the 32-channel layers and the 64-channel k <= 3 layers,
 // whose few reduction stages per tile leave the prologue / epilogue exposed.
 static bool wanted(const VcvConvArgs& a) {
-  if (g_all) return true;
+  if (vcv_tuning().x3_all) return true;
   if (a.Cg <= 32) return false;
   if (a.Cg <= 64 && a.K <= 3) return false;
   return true;
@@ -783,7 +782,7 @@ static int run(const VcvConvArgs* args, float* pack_ws, float* scratch_ws, int f
     for (int i = 0; i < 16; ++i) desc[i] = d[i];
   }
   hipStream_t st = (hipStream_t)stream;
-  return g_terms == 6 ? run_n<6>(*args, pl, (char*)pack_ws, scratch_ws, flip, pack_valid != 0, st, desc)
+  return vcv_tuning().x3_terms == 6 ? run_n<6>(*args, pl, (char*)pack_ws, scratch_ws, flip, pack_valid != 0, st, desc)
                       : run_n<9>(*args, pl, (char*)pack_ws, scratch_ws, flip, pack_valid != 0, st, desc);
 }
 
