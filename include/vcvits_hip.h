@@ -452,6 +452,24 @@ int vcv_set_words(void* dst, int n, int w0, int w1, int w2, int w3, void* stream
 int vcv_adamw_dev(float* p, const float* g, float* m, float* v, int64_t n, float b1, float b2, float eps, float wd,
                   const void* hyper_dev, int step_base, void* stream);
 
+/* ---- gradient norms of segments of a flat fp32 buffer, and AdamW with a clip coefficient read from device memory
+ * (torch.nn.utils.clip_grad_norm_ / Lightning's gradient_clip_val; the logged grad_norm_* of vcvits.py:119,162-163) ----
+ * segs_dev: S <= 8 pairs of int64 element offsets (lo, hi) in DEVICE memory; a segment may start and end at any element, an
+ * empty one (hi <= lo) yields 0, and no element outside a segment is read.  Squares and sums are formed in fp64 by two
+ * launches without atomics: per-workgroup partials into `ws` (S * 1024 doubles), then one workgroup adds them in index order.
+ * The results are bit-reproducible and the call can be recorded into a HIP graph (nothing is allocated, nothing waits).
+ * rec (12 * S + 8 bytes, 8-byte aligned): double sq[S]; float norm[S]; float total_norm (the square root of the fp64 sum
+ * of sq[]); float coef = min(1, max_norm / (total_norm + 1e-6)) in fp32 -- exactly 1.0f when max_norm <= 0, +inf or NaN
+ * ("do not clip").  NaN / inf in the buffer propagate as IEEE arithmetic gives them (torch: error_if_nonfinite=False).
+ * The caller guarantees 0 <= lo, hi <= the buffer's length: the table is not read on the host. */
+int vcv_grad_sqnorm(const float* buf, const void* segs_dev, int S, void* ws, void* rec, float max_norm, void* stream);
+/* vcv_adamw / vcv_adamw_dev on g' = g * coef_dev[0] (rounded once to fp32); g itself is not written.  coef == 1.0f gives the
+ * bits of vcv_adamw / vcv_adamw_dev. */
+int vcv_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
+                   float wd, int step, const float* coef_dev, void* stream);
+int vcv_adamw_dev_clip(float* p, const float* g, float* m, float* v, int64_t n, float b1, float b2, float eps, float wd,
+                       const void* hyper_dev, int step_base, const float* coef_dev, void* stream);
+
 /* ---- STFT magnitude sqrt(re^2+im^2+eps) (mel_processing.py:54-96): n_fft = 2048 (both reference configs; the tuned
  * kernels), any other power of two in [64, 4096] (generic radix-2 kernels) or any other even size in [16, 4096] (direct DFT;
  * stft_generic.hip).

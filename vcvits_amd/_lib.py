@@ -116,6 +116,7 @@ EXPORTS = [
     "vcv_rel_attn_stream_supported", "vcv_rel_attn_stream_fwd",
     "vcv_rel_attn_stream_train_fwd", "vcv_rel_attn_stream_bwd_workspace", "vcv_rel_attn_stream_bwd",
     "vcv_rel_attn_stream_fwd_bf16", "vcv_hubert_attn_fwd_bf16", "vcv_hubert_attn_fwd_len_bf16",
+    "vcv_grad_sqnorm", "vcv_adamw_clip", "vcv_adamw_dev_clip",
 ]
 
 
@@ -240,6 +241,9 @@ _ARGTYPES = {
     "vcv_embedding_t_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vcv_set_words": [_P, _I, _I, _I, _I, _I, _P],
     "vcv_adamw_dev": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _P, _I, _P],
+    "vcv_grad_sqnorm": [_P, _P, _I, _P, _P, _F, _P],
+    "vcv_adamw_clip": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P, _P],
+    "vcv_adamw_dev_clip": [_P, _P, _P, _P, _L, _F, _F, _F, _F, _P, _I, _P, _P],
     "vcv_conv_bf16io_plan": [ctypes.POINTER(VcvConvArgs), _I, ctypes.POINTER(ctypes.c_int64)],
     "vcv_conv_bf16io_run": [ctypes.POINTER(VcvConvArgs), _P, _P, _I, _I, _P],
     "vcv_prof_active": [],

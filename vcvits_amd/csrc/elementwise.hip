@@ -434,6 +434,169 @@ __global__ void adamw_dev_kernel(float* __restrict__ p, const float* __restrict_
   p[i] = pi; m[i] = mi; v[i] = vi;
 }
 
+// ---- gradient norms of segments of the flat gradient buffer + AdamW with a clip coefficient from device memory ----------
+// (torch.nn.utils.clip_grad_norm_ and the reference's logged grad_norm_*, vits/light/vcvits.py:119,162-163, without a
+// reduction per parameter tensor and without a host sync.)  Two launches, no atomics: the result is bit-reproducible and the
+// pair can be recorded into a HIP graph.  Squares and sums are fp64: the square of an fp32 value is exact there.
+//
+// Stage one: workgroup b of segment s (grid = GN_MAXB x S) sweeps the 16-byte-aligned body of buf[lo, hi) with float4 loads,
+// GN_UNROLL of them in flight per thread, and writes ONE fp64 partial to ws[s * GN_MAXB + b]; workgroup 0 also takes the
+// <= 3 elements in front of the body and the <= 3 behind it with scalar loads, so nothing outside [lo, hi) is ever read.
+// The table lives in device memory (the host cannot size the grid by it): a segment of n4 float4s uses the first
+// gn_blocks(n4) workgroups of its row -- as vcv_loss_sum caps its grid -- and the others leave at once.
+constexpr int GN_MAXB = 1024;   // workgroups (= partials) per segment
+constexpr int GN_UNROLL = 4;    // float4 loads in flight per thread: one pass of a workgroup covers 256 * 4 * 4 floats
+constexpr int GN_MAXS = 8;      // segments per call
+
+__device__ __forceinline__ int gn_blocks(long long n4, int head_tail) {
+  const long long per = 256LL * GN_UNROLL;
+  long long nb = (n4 + per - 1) / per;
+  if (nb > GN_MAXB) nb = GN_MAXB;
+  if (nb < 1 && head_tail > 0) nb = 1;
+  return (int)nb;
+}
+
+// the pieces of segment [lo, hi): `head` scalars, n4 float4s from element lo + head on, `tail` scalars
+__device__ __forceinline__ void gn_split(const float* buf, long long lo, long long hi, int& head, long long& n4, int& tail) {
+  const long long n = hi > lo ? hi - lo : 0;
+  const int mis = (int)((((uintptr_t)(buf + lo)) >> 2) & 3);  // floats past a 16-byte boundary
+  long long h = (4 - mis) & 3;
+  if (h > n) h = n;
+  head = (int)h;
+  n4 = (n - h) >> 2;
+  tail = (int)(n - h - (n4 << 2));
+}
+
+__device__ __forceinline__ double gn_sq4(const float4 a) {
+  const double x = a.x, y = a.y, z = a.z, w = a.w;
+  return (x * x + y * y) + (z * z + w * w);
+}
+
+__device__ __forceinline__ double wave_sum_f64(double s) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+  return s;
+}
+
+__global__ void __launch_bounds__(256)
+grad_sqnorm_partial_kernel(const float* __restrict__ buf, const long long* __restrict__ segs, double* __restrict__ ws) {
+  __shared__ double red[4];
+  const int s = blockIdx.y, b = blockIdx.x;
+  const long long lo = segs[2 * s], hi = segs[2 * s + 1];
+  int head, tail;
+  long long n4;
+  gn_split(buf, lo, hi, head, n4, tail);
+  const int nb = gn_blocks(n4, head + tail);
+  if (b >= nb) return;  // (uniform per workgroup: before any barrier)
+  double acc = 0.0;
+  if (b == 0) {
+    const int t = threadIdx.x;
+    if (t < head) { const double x = buf[lo + t]; acc = x * x; }
+    else if (t >= 4 && t - 4 < tail) { const double x = buf[lo + head + (n4 << 2) + (t - 4)]; acc = x * x; }
+  }
+  const float4* __restrict__ p = (const float4*)(buf + lo + head);
+  const long long stride = (long long)nb * 256 * GN_UNROLL;
+  for (long long i0 = (long long)b * 256 * GN_UNROLL + threadIdx.x; i0 < n4; i0 += stride) {
+    float4 v[GN_UNROLL];
+#pragma unroll
+    for (int u = 0; u < GN_UNROLL; ++u) {
+      const long long i = i0 + u * 256;
+      v[u] = i < n4 ? p[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < GN_UNROLL; ++u) acc += gn_sq4(v[u]);
+  }
+  acc = wave_sum_f64(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) ws[(size_t)s * GN_MAXB + b] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// Finishing stage, one workgroup: the partials of every segment are read into LDS by all threads (coalesced), then thread s
+// adds segment s's partials IN INDEX ORDER (a fixed order: the bits of the result do not depend on scheduling), and thread 0
+// forms the total over the segments, also in index order, and the clip coefficient.  The record: double sq[S]; float
+// norm[S]; float total_norm; float coef.
+__global__ void __launch_bounds__(256)
+grad_sqnorm_finish_kernel(const float* __restrict__ buf, const long long* __restrict__ segs, int S,
+                          const double* __restrict__ ws, unsigned char* __restrict__ rec, float max_norm) {
+  __shared__ double part[GN_MAXB * GN_MAXS];  // part[i * S + s]: the S threads that add read consecutive words (64 KB)
+  int nb_mine = 0;
+  for (int s = 0; s < S; ++s) {
+    int head, tail;
+    long long n4;
+    gn_split(buf, segs[2 * s], segs[2 * s + 1], head, n4, tail);
+    const int nb = gn_blocks(n4, head + tail);  // (the workgroups of stage one that wrote a partial)
+    if (s == (int)threadIdx.x) nb_mine = nb;
+    for (int i = threadIdx.x; i < nb; i += 256) part[i * S + s] = ws[(size_t)s * GN_MAXB + i];
+  }
+  __syncthreads();
+  double* sq = (double*)rec;
+  float* norm = (float*)(rec + 8 * (size_t)S);
+  double acc = 0.0;
+  if ((int)threadIdx.x < S)
+    for (int i = 0; i < nb_mine; ++i) acc += part[i * S + threadIdx.x];
+  __syncthreads();  // (every partial has been read: the first S words now carry the segment sums to thread 0)
+  if ((int)threadIdx.x < S) {
+    part[threadIdx.x] = acc;
+    sq[threadIdx.x] = acc;
+    norm[threadIdx.x] = (float)sqrt(acc);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tot = 0.0;
+    for (int s = 0; s < S; ++s) tot += part[s];
+    const float total = (float)sqrt(tot);
+    float coef = 1.f;
+    if (max_norm > 0.f && max_norm < __builtin_huge_valf()) {
+      // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (total_norm + 1e-6), max=1.0) in fp32; a NaN stays a NaN
+      const float c = max_norm / (total + 1e-6f);
+      coef = c > 1.f ? 1.f : c;
+    }
+    norm[S] = total;
+    norm[S + 1] = coef;
+  }
+}
+
+// one AdamW update of element i with the gradient scaled by the clip coefficient: g' = g * coef, rounded once to fp32, then
+// the body of adamw_kernel / adamw_dev_kernel word for word (coef == 1.0f gives their bits).  g itself is not written.
+__device__ __forceinline__ void adamw_clip_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                  float* __restrict__ v, size_t i, float coef, float lr, float b1, float b2,
+                                                  float eps, float wd, float bc1, float bc2_sqrt) {
+  const float gi = g[i] * coef;
+  float pi = p[i] * (1.f - lr * wd);
+  const float mi = b1 * m[i] + (1.f - b1) * gi;
+  const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+  const float denom = sqrtf(vi) / bc2_sqrt + eps;
+  pi -= (lr / bc1) * (mi / denom);
+  p[i] = pi; m[i] = mi; v[i] = vi;
+}
+
+__global__ void adamw_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                  float* __restrict__ v, size_t n, float lr, float b1, float b2, float eps, float wd,
+                                  float bc1, float bc2_sqrt, const float* __restrict__ coef_dev) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  adamw_clip_update(p, g, m, v, i, coef_dev[0], lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+}
+
+__global__ void adamw_dev_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                      float* __restrict__ v, size_t n, float b1, float b2, float eps, float wd,
+                                      const int* __restrict__ hyper, int step_base, const float* __restrict__ coef_dev) {
+  __shared__ float s_h[3];
+  if (threadIdx.x == 0) {
+    const int step = step_base + hyper[1];
+    const double bc1 = 1.0 - pow((double)b1, (double)step);
+    const double bc2 = 1.0 - pow((double)b2, (double)step);
+    s_h[0] = __int_as_float(hyper[0]);
+    s_h[1] = (float)bc1;
+    s_h[2] = (float)sqrt(bc2);
+  }
+  __syncthreads();
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  adamw_clip_update(p, g, m, v, i, coef_dev[0], s_h[0], b1, b2, eps, wd, s_h[1], s_h[2]);
+}
+
 __global__ void set_words_kernel(int* __restrict__ dst, int n, int w0, int w1, int w2, int w3) {
   const int w[4] = {w0, w1, w2, w3};
   if ((int)threadIdx.x < n) dst[threadIdx.x] = w[threadIdx.x];
@@ -642,5 +805,37 @@ extern "C" int vcv_adamw(float* p, const float* g, float* m, float* v, int64_t n
   const double bc2 = 1.0 - pow((double)b2, (double)step);
   hipLaunchKernelGGL(adamw_kernel, grid1d(n), dim3(256), 0, ST, p, g, m, v, (size_t)n, lr, b1, b2, eps, wd,
                      (float)bc1, (float)sqrt(bc2));
+  return vcv_check_launch();
+}
+
+// buf[segs[s][0], segs[s][1]) for s < S (int64 element offsets, device memory): squared L2 norms into `rec` (layout above,
+// 12 * S + 8 bytes, 8-byte aligned), through `ws` (S * 1024 doubles).  Both are the caller's; nothing is allocated, nothing
+// waits: the two launches can be recorded into a HIP graph.  max_norm <= 0, +inf or NaN: no clipping, coef = 1.0f exactly.
+extern "C" int vcv_grad_sqnorm(const float* buf, const void* segs_dev, int S, void* ws, void* rec, float max_norm,
+                               void* stream) {
+  if (!buf || !segs_dev || !ws || !rec || S <= 0 || S > GN_MAXS) return VCV_EINVAL;
+  if ((((uintptr_t)buf) & 3) || (((uintptr_t)ws | (uintptr_t)rec | (uintptr_t)segs_dev) & 7)) return VCV_EINVAL;
+  hipLaunchKernelGGL(grad_sqnorm_partial_kernel, dim3(GN_MAXB, S), dim3(256), 0, ST, buf, (const long long*)segs_dev,
+                     (double*)ws);
+  hipLaunchKernelGGL(grad_sqnorm_finish_kernel, dim3(1), dim3(256), 0, ST, buf, (const long long*)segs_dev, S,
+                     (const double*)ws, (unsigned char*)rec, max_norm);
+  return vcv_check_launch();
+}
+
+extern "C" int vcv_adamw_dev_clip(float* p, const float* g, float* m, float* v, int64_t n, float b1, float b2, float eps,
+                                  float wd, const void* hyper_dev, int step_base, const float* coef_dev, void* stream) {
+  if (!p || !g || !m || !v || !hyper_dev || !coef_dev || n <= 0 || step_base <= 0) return VCV_EINVAL;
+  hipLaunchKernelGGL(adamw_dev_clip_kernel, grid1d(n), dim3(256), 0, ST, p, g, m, v, (size_t)n, b1, b2, eps, wd,
+                     (const int*)hyper_dev, step_base, coef_dev);
+  return vcv_check_launch();
+}
+
+extern "C" int vcv_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2,
+                              float eps, float wd, int step, const float* coef_dev, void* stream) {
+  if (!p || !g || !m || !v || !coef_dev || n <= 0 || step <= 0) return VCV_EINVAL;
+  const double bc1 = 1.0 - pow((double)b1, (double)step);
+  const double bc2 = 1.0 - pow((double)b2, (double)step);
+  hipLaunchKernelGGL(adamw_clip_kernel, grid1d(n), dim3(256), 0, ST, p, g, m, v, (size_t)n, lr, b1, b2, eps, wd,
+                     (float)bc1, (float)sqrt(bc2), coef_dev);
   return vcv_check_launch();
 }

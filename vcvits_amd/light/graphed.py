@@ -333,7 +333,9 @@ class GraphedBatch(_Recorder):
         if not self.applicable():
             return None
         m = self.module
-        key = _shape_key(batch) + tuple(extra) + (ops.GRAPH_EPOCH[0], id(m.optim_g), id(m.optim_d))
+        # (the gradient-norm / clip settings: the norm launch, the `_clip` form of the steps and max_grad_norm are baked)
+        key = _shape_key(batch) + tuple(extra) + (ops.GRAPH_EPOCH[0], id(m.optim_g), id(m.optim_d)) + \
+            tuple((getattr(o, "max_grad_norm", None), getattr(o, "log_norms", False)) for o in (m.optim_g, m.optim_d))
         ent, record = self._lookup(key)
         if ent is None:
             if not record:
@@ -385,6 +387,7 @@ class GraphedBatch(_Recorder):
             opt.static_check()  # (data parallel: the periodic "did any rank's used-parameter set change" byte)
         ops.invalidate_weights()  # the recorded AdamW steps wrote the parameters
         m.logged = ent["logged"]
+        m._logged_g = ent["logged_g"]
         self.replays += 1
         return ent["losses"]
 
@@ -503,7 +506,11 @@ class GraphedBatch(_Recorder):
             return None
         graph, cap, seed, losses = rec
         cap.append(arena["buf"])
+        # gradient norms / clip coefficients (when switched on): views of the optimizers' device records, which the recorded
+        # norm launches rewrite at every replay -- static tensors like the losses
+        losses.update(m._norm_outputs())
         ent = {"graph": graph, "inputs": static, "losses": losses, "seed": seed, "cap": cap, "logged": dict(m.logged), "root": root_one,
+               "logged_g": dict(getattr(m, "_logged_g", {})),
                "device": dev, "bytes": self.last_pool_bytes + 4 * int(arena["buf"].numel()), "segments": segments,
                "touched_g": state["touched_g"], "touched_d": state["touched_d"],
                "ranges_g": state["ranges_g"], "ranges_d": state["ranges_d"],

@@ -56,10 +56,21 @@ class FlatAdamW(torch.optim.Optimizer):
     A `torch.optim.Optimizer` (one parameter group), so what consumes the reference's `configure_optimizers`
     (vits/light/vcvits.py:247-263 returns two torch.optim.AdamW to Lightning, which type-checks them) accepts it:
     `param_groups[0]["lr"]` is the live learning rate (an external scheduler may write it), `step(closure)` runs the
-    closure first as Lightning's automatic optimisation does, `zero_grad()` keeps the permanent gradient views."""
+    closure first as Lightning's automatic optimisation does, `zero_grad()` keeps the permanent gradient views.
+
+    Gradient norms and clipping by global norm (off by default; with both off `step()` is the code path it always was):
+    `norm_segments` names groups of parameters -- [(name, parameters), ...], each one contiguous range of the flat buffer, the
+    groups together covering it; default one group "all" -- whose L2 gradient norms one device reduction (ops.grad_sqnorm:
+    two launches, fp64, no atomics, no host sync, capturable) writes into a device record at every step once `log_norms` is
+    set or `max_grad_norm` is a positive number.  With `max_grad_norm` set the step then runs on g * coef with
+    coef = min(1, max_grad_norm / (total norm + 1e-6)) read from that record (torch.nn.utils.clip_grad_norm_ over this
+    optimizer's parameters, as Lightning's `gradient_clip_val` clips per optimizer); the gradient buffer itself keeps the
+    unclipped gradient.  The reduction runs after `finish_grad_sync()`: under data parallelism it is the norm of the
+    all-reduced gradient, the same bits on every rank, so every rank scales by the same coefficient.  `grad_norms()` returns
+    views of the record.  Both settings are runtime state: they are not part of `state_dict()`."""
 
     def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, bucket_mb=32,
-                 process_group=None):
+                 process_group=None, max_grad_norm=None, norm_segments=None):
         params = [p for p in params]
         if not params:
             raise ValueError("FlatAdamW: empty parameter list")
@@ -90,6 +101,13 @@ class FlatAdamW(torch.optim.Optimizer):
         self.step_count = 0
         self.hyper = None  # device record {lr, step delta} of optimizer steps recorded into a HIP graph (step())
         self.captured_ranges = None
+        # gradient norms / clipping: the segment table is checked here (host side); the device table, the workspace and the
+        # record are allocated ONCE, when either setting is first switched on (recorded graphs bake their addresses)
+        self._norm_names, self._norm_ranges = self._check_norm_segments(norm_segments)
+        self._norm_state = None
+        self._max_grad_norm = None
+        self._log_norms = False
+        self.max_grad_norm = max_grad_norm
         # (the reference reads optim_g.param_groups[0]['lr'], vcvits.py:122: torch's own group dict, kept in step with self.lr)
         # ---- data parallel ----
         self.pg = process_group
@@ -282,6 +300,94 @@ class FlatAdamW(torch.optim.Optimizer):
                                "it was frozen (static-graph mode)%s; set VCVITS_DDP_STATIC=0 for models whose "
                                "used-parameter set varies from step to step" % (" -- on this rank" if self._violation else ""))
 
+    # -- gradient norms / clipping by global norm ---------------------------------------------------
+    def _check_norm_segments(self, norm_segments):
+        """(names, [(lo, hi)]) of the named parameter groups as element ranges of the flat buffer."""
+        if norm_segments is None:
+            return ["all"], [(0, self.numel)]
+        index = {id(p): i for i, p in enumerate(self.params)}
+        names, ranges, seen = [], [], set()
+        for name, group in norm_segments:
+            if name in ("total", "coef") or name in names:
+                raise ValueError("FlatAdamW: norm segment name %r is reserved or repeated" % (name,))
+            try:
+                idx = sorted(index[id(p)] for p in group)
+            except KeyError:
+                raise ValueError("FlatAdamW: norm segment %r holds a parameter this optimizer does not own" % (name,)) from None
+            if not idx:
+                raise ValueError("FlatAdamW: norm segment %r is empty" % (name,))
+            if idx != list(range(idx[0], idx[-1] + 1)):
+                raise ValueError("FlatAdamW: the parameters of norm segment %r are not one contiguous range of the flat buffer "
+                                 "(parameters are stored in reverse registration order)" % (name,))
+            if seen.intersection(idx):
+                raise ValueError("FlatAdamW: norm segment %r shares a parameter with another segment" % (name,))
+            seen.update(idx)
+            names.append(name)
+            ranges.append((self.offsets[idx[0]], self.offsets[idx[-1]] + self.params[idx[-1]].numel()))
+        if len(seen) != len(self.params):
+            raise ValueError("FlatAdamW: the norm segments leave out %d of %d parameters (the clip coefficient is formed from "
+                             "their total: they must cover the optimizer)" % (len(self.params) - len(seen), len(self.params)))
+        if len(names) > ops.GRAD_SQNORM_MAX_SEGMENTS:
+            raise ValueError("FlatAdamW: at most %d norm segments" % ops.GRAD_SQNORM_MAX_SEGMENTS)
+        return names, ranges
+
+    @property
+    def max_grad_norm(self):
+        """None (off) or the positive L2 norm this optimizer's gradient is clipped to before the step."""
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        if value is not None:
+            value = float(value)
+            if value != value or value < 0:
+                raise ValueError("FlatAdamW: max_grad_norm must be None or a number >= 0, got %r" % (value,))
+            if value == 0 or value == float("inf"):
+                value = None  # (Lightning: gradient_clip_val 0 / None is "off")
+        self._max_grad_norm = value
+        if value is not None:
+            self._ensure_norm_state()
+
+    @property
+    def log_norms(self):
+        """Whether `step()` computes the gradient norms although it does not clip."""
+        return self._log_norms
+
+    @log_norms.setter
+    def log_norms(self, on):
+        self._log_norms = bool(on)
+        if self._log_norms:
+            self._ensure_norm_state()
+
+    def norms_enabled(self):
+        return self._max_grad_norm is not None or self._log_norms
+
+    def _ensure_norm_state(self):
+        if self._norm_state is not None or not self.flat.is_cuda:
+            return  # (CPU parameters: step() refuses them anyway)
+        if ops.CAPTURING[0] is not None:
+            raise RuntimeError("FlatAdamW: gradient norms were switched on while a HIP graph is being recorded")
+        S, dev = len(self._norm_names), self.flat.device
+        for lo, hi in self._norm_ranges:
+            assert 0 <= lo <= hi <= self.numel
+        segs = torch.tensor([v for r in self._norm_ranges for v in r], dtype=torch.int64).to(dev)
+        ws = torch.zeros(S * ops.GRAD_SQNORM_WS_PER_SEGMENT, device=dev, dtype=torch.float64)
+        rec = torch.zeros((ops.grad_sqnorm_record_bytes(S) + 7) // 8 * 8, device=dev, dtype=torch.uint8)
+        norm = rec[8 * S:12 * S].view(torch.float32)
+        views = {name: norm[i] for i, name in enumerate(self._norm_names)}
+        views["total"] = rec[12 * S:12 * S + 4].view(torch.float32)[0]
+        views["coef"] = rec[12 * S + 4:12 * S + 8].view(torch.float32)[0]
+        views["coef"].fill_(1.0)
+        self._norm_state = {"segs": segs, "ws": ws, "rec": rec, "views": views, "sq": rec[:8 * S].view(torch.float64)}
+
+    def grad_norms(self):
+        """{segment name: 0-d fp32 device tensor} plus "total" (the norm over all segments) and "coef" (the clip coefficient
+        the last step used; 1.0 without clipping): views of the device record the last `step()` wrote, pre-clip norms of the
+        gradient that step consumed.  Reading them here costs no sync; their values change at the next step."""
+        if self._norm_state is None:
+            raise RuntimeError("FlatAdamW.grad_norms: neither max_grad_norm nor log_norms is set (or the parameters are not on the GPU)")
+        return dict(self._norm_state["views"])
+
     # -- optimizer ---------------------------------------------------------------------------------
     def zero_grad(self, set_to_none=False):
         self.grad.zero_()
@@ -322,7 +428,9 @@ class FlatAdamW(torch.optim.Optimizer):
         if not self.flat.is_cuda:
             raise RuntimeError("FlatAdamW.step: parameters are not on the GPU (no CPU fallback)")
         ranges = self._update_ranges()
-        if ops.CAPTURING[0] is not None:
+        if self.norms_enabled():
+            self._step_clipped(ranges)
+        elif ops.CAPTURING[0] is not None:
             # recorded into a HIP graph (light/graphed.py): the learning rate and the step count come from a device record
             # the host refreshes before each replay; `captured_ranges` lets the replay work out the step delta
             if self.hyper is None:
@@ -338,6 +446,25 @@ class FlatAdamW(torch.optim.Optimizer):
         # the kernel wrote the parameters through raw pointers: drop weights derived from them
         ops.invalidate_weights(self.flat.data_ptr(), self.flat.data_ptr() + 4 * self.numel)
         return loss
+
+    def _step_clipped(self, ranges):
+        """The norm reduction over the (all-reduced) gradient buffer, then the AdamW launches of step() in their `_clip` form:
+        eager and recorded alike."""
+        self._ensure_norm_state()
+        st = self._norm_state
+        ops.grad_sqnorm(self.grad, st["segs"], len(self._norm_names), st["ws"], st["rec"], self._max_grad_norm or 0.0)
+        coef = st["views"]["coef"]
+        if ops.CAPTURING[0] is not None:
+            if self.hyper is None:
+                self.hyper = torch.zeros(2, device=self.flat.device, dtype=torch.int32)
+            for lo, hi, st_, _i in ranges:
+                ops.adamw_step_dev_clip(self.flat[lo:hi], self.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
+                                        self.betas, self.eps, self.weight_decay, self.hyper, st_, coef)
+            self.captured_ranges = [(i, st_) for _lo, _hi, st_, i in ranges]
+        else:
+            for lo, hi, st_, _i in ranges:
+                ops.adamw_step_clip(self.flat[lo:hi], self.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], self.lr,
+                                    self.betas, self.eps, self.weight_decay, st_, coef)
 
     def set_lr(self, lr):
         self.lr = float(lr)

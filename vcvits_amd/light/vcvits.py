@@ -51,6 +51,24 @@ except Exception:  # noqa: BLE001 -- not installed (this image) or broken: the m
 
 from ..model.discriminators._pair import join_streams  # noqa: E402
 
+
+def parse_gradient_clip(gradient_clip_val, gradient_clip_algorithm=None):
+    """Lightning's `gradient_clip_val` / `gradient_clip_algorithm` (the reference hands `hparams.trainer` to `pl.Trainer`,
+    train.py:102) -> None (off: None or 0) or the positive L2 norm to clip to.  Only clipping by norm is built."""
+    if gradient_clip_algorithm is not None:
+        alg = str(getattr(gradient_clip_algorithm, "value", gradient_clip_algorithm)).lower()
+        if alg == "value":
+            raise NotImplementedError("gradient_clip_algorithm='value': only clipping by global norm ('norm') is implemented")
+        if alg != "norm":
+            raise ValueError("gradient_clip_algorithm must be 'norm', got %r" % (gradient_clip_algorithm,))
+    if gradient_clip_val is None:
+        return None
+    val = float(gradient_clip_val)
+    if val != val or val < 0:
+        raise ValueError("gradient_clip_val must be None or a number >= 0, got %r" % (gradient_clip_val,))
+    return val if val > 0 else None
+
+
 class VCVITS(_Base):
     def __init__(self, **kwargs):
         super().__init__()
@@ -77,6 +95,9 @@ class VCVITS(_Base):
         self._own_epoch = 0
         self._own_step = 0
         self.logged = {}
+        self._logged_g = {}  # the generator branch's scalars of the last batch (`logged` is replaced by each branch)
+        self._norm_options()  # (a bad gradient_clip_val / gradient_clip_algorithm fails here, not at the first batch)
+        self._norm_applied = None
         self.optim_g = self.optim_d = None
         self.scheduler_g = self.scheduler_d = None
 
@@ -102,6 +123,76 @@ class VCVITS(_Base):
     @global_step.setter
     def global_step(self, v):
         self._own_step = int(v)
+
+    # ------------------------------------------------------------------------------------------
+    # gradient norms / clipping by global norm (both off by default)
+    def _norm_options(self):
+        """(clip value or None, log_grad_norms) from `hparams.trainer.gradient_clip_val` (+ `gradient_clip_algorithm`) and
+        `hparams.train.log_grad_norms`."""
+        def opt(obj, key, default=None):  # (HParams, Lightning's AttributeDict, a plain dict or a namespace)
+            return obj.get(key, default) if hasattr(obj, "get") else getattr(obj, key, default)
+
+        hp = self.hparams
+        tr = opt(hp, "trainer") or {}
+        clip = parse_gradient_clip(opt(tr, "gradient_clip_val"), opt(tr, "gradient_clip_algorithm"))
+        return clip, bool(opt(hp.train, "log_grad_norms", False) or False)
+
+    def _apply_norm_options(self):
+        """Hand the two options to the optimizers whenever the hparams' values changed since they were last applied (a value
+        written to an optimizer directly -- `configure_gradient_clipping` under a Lightning Trainer -- stays otherwise)."""
+        opts = self._norm_options()
+        if opts != self._norm_applied:
+            for o in (self.optim_g, self.optim_d):
+                o.max_grad_norm, o.log_norms = opts
+            self._norm_applied = opts
+
+    def _norm_outputs(self):
+        """The entries `fit_batch` adds while norms are computed: 0-d device views of the optimizers' records (the pre-clip
+        norms of the batch just run; valid until the next batch, like the losses of a replayed one)."""
+        out = {}
+        og, od = self.optim_g, self.optim_d
+        if og is not None and og.norms_enabled():
+            v = og.grad_norms()
+            out["grad_norm_g"] = v["net_g"]
+            if og.max_grad_norm is not None:
+                out["clip_coef_g"] = v["coef"]
+        if od is not None and od.norms_enabled():
+            v = od.grad_norms()
+            out["grad_norm_p_d"], out["grad_norm_s_d"] = v["net_period_d"], v["net_scale_d"]
+            if od.max_grad_norm is not None:
+                out["clip_coef_d"] = v["coef"]
+        return out
+
+    def training_scalars(self):
+        """The reference's two `scalar_dict`s (vcvits.py:119-131, 162-171) of the LAST batch as Python floats: both branches'
+        loss terms, `learning_rate` and, when they are computed, the gradient norms (and clip coefficients).  One device ->
+        host copy, i.e. one sync: call it at `log_interval`, not every step.  The norms are those of the batch just run; the
+        reference reads `p.grad` before that step's backward pass, so its logged norm is the previous step's."""
+        tensors = dict(self._logged_g)
+        tensors.update(self.logged)
+        if not tensors:
+            raise RuntimeError("training_scalars: no batch has run yet")
+        tensors.update(self._norm_outputs())
+        names = list(tensors)
+        vals = torch.stack([tensors[k].detach().reshape(()).float() for k in names]).cpu().tolist()
+        out = dict(zip(names, vals))
+        out["learning_rate"] = float(self.optim_g.param_groups[0]["lr"])  # (vcvits.py:122,166: optim_g's in both branches)
+        return out
+
+    def configure_gradient_clipping(self, optimizer, optimizer_idx=None, gradient_clip_val=None, gradient_clip_algorithm=None):
+        """Lightning's hook: the Trainer's `gradient_clip_val` lands in the flat optimizer's `max_grad_norm` (one device
+        reduction and a coefficient the step reads) instead of torch's per-tensor `clip_grad_norm_`."""
+        # Lightning calls the hook with keywords.  Called positionally, 2.x has no optimizer_idx -- (optimizer, clip value,
+        # algorithm) -- which shows as a second argument that is no int, or a third that is an algorithm, not a number
+        def is_algorithm(v):
+            return hasattr(v, "value") or (isinstance(v, str) and not v.replace(".", "", 1).replace("e-", "", 1).isdigit())
+        if optimizer_idx is not None and (isinstance(optimizer_idx, bool) or not isinstance(optimizer_idx, int)
+                                          or (gradient_clip_algorithm is None and is_algorithm(gradient_clip_val))):
+            optimizer_idx, gradient_clip_val, gradient_clip_algorithm = None, optimizer_idx, gradient_clip_val
+        opt = optimizer if isinstance(optimizer, FlatAdamW) else getattr(optimizer, "optimizer", optimizer)
+        if not isinstance(opt, FlatAdamW):
+            raise TypeError("configure_gradient_clipping: %s is not one of this module's FlatAdamW optimizers" % type(opt).__name__)
+        opt.max_grad_norm = parse_gradient_clip(gradient_clip_val, gradient_clip_algorithm)
 
     def set_feature_extractor(self, extractor):
         """Plug the frozen HuBERT (or any stand-in with its `extract_features` contract) into the content encoder."""
@@ -218,6 +309,7 @@ class VCVITS(_Base):
                 loss_gen_all = loss_gen_all + loss_kl
                 self.logged["loss/g/loss_kl"] = loss_kl
             self.logged["loss/g/total"] = loss_gen_all
+            self._logged_g = self.logged
             return loss_gen_all
         if optimizer_idx == 1:
             with torch.no_grad():  # only y_hat.detach() is consumed (vcvits.py:153,157)
@@ -228,6 +320,10 @@ class VCVITS(_Base):
             loss_disc_s, r_s, g_s = discriminator_loss(y_ds_hat_r, y_ds_hat_g)
             loss_disc_all = loss_disc_p + loss_disc_s
             self.logged = {"loss/d/total": loss_disc_all}
+            # the per-sub-discriminator terms under the reference's names (vcvits.py:168-171): views of the two term vectors
+            for name, terms in (("d_p_r", r_p), ("d_p_g", g_p), ("d_s_r", r_s), ("d_s_g", g_s)):
+                for i, v in enumerate(terms):
+                    self.logged["loss/%s/%d" % (name, i)] = v
             return loss_disc_all
         raise ValueError("optimizer_idx must be 0 (generator) or 1 (discriminators)")
 
@@ -303,10 +399,16 @@ class VCVITS(_Base):
         import torch.distributed as dist
         rank = dist.get_rank(process_group) if dist.is_available() and dist.is_initialized() else 0
         ops.manual_seed(torch.initial_seed() + 7919 * rank)
+        # norm segments: what the reference logs as grad_norm_g / grad_norm_p_d / grad_norm_s_d (vcvits.py:119,162-163); a
+        # clipped step uses each optimizer's total, as Lightning clips per optimizer.  Nothing runs until an option is set.
         self.optim_g = FlatAdamW(self.generator_parameters(), t.learning_rate, betas=t.betas, eps=t.eps,
-                                 process_group=process_group)
+                                 process_group=process_group, norm_segments=[("net_g", list(self.generator_parameters()))])
         self.optim_d = FlatAdamW(itertools.chain(self.net_period_d.parameters(), self.net_scale_d.parameters()),
-                                 t.learning_rate, betas=t.betas, eps=t.eps, process_group=process_group)
+                                 t.learning_rate, betas=t.betas, eps=t.eps, process_group=process_group,
+                                 norm_segments=[("net_period_d", list(self.net_period_d.parameters())),
+                                                ("net_scale_d", list(self.net_scale_d.parameters()))])
+        self._norm_applied = None
+        self._apply_norm_options()
         # vcvits.py:258-261: ExponentialLR per optimizer with last_epoch re-seated to current_epoch - 1 (the rate
         # itself starts at learning_rate; a resume restores it with the optimizer state)
         # (`train.lr_reference_stack` in the hparams selects the scheduler semantics: see ExponentialLR)
@@ -362,6 +464,7 @@ class VCVITS(_Base):
 
     def _fit_batch_inner(self, batch, batch_idx=0, after_backward=None):
         batch = self._bucketed(batch)
+        self._apply_norm_options()
         if after_backward is None:
             # the whole batch -- both passes and their AdamW steps -- replayed from ONE HIP graph once the batch shapes
             # repeat (light/graphed.py); None: run it eagerly (shapes still new, profiler active, graphs off)
@@ -388,6 +491,7 @@ class VCVITS(_Base):
             out["g" if idx == 0 else "d"] = loss.detach()
         for p in itertools.chain(self.optim_g.params, self.optim_d.params):
             p.requires_grad_(True)
+        out.update(self._norm_outputs())
         self._own_step += 1
         return out
 
